@@ -9,7 +9,9 @@ density-grid refresh every 16 steps.  Multi-GPU: one process per GPU, each
 rank renders its own seed (data parallel over views), gradients all-reduced
 over RCCL before the optimizer step (weak scaling).
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run
+sets up, warms up, times --steps steps, writes --dump-outputs if asked and
+prints the headline; --full adds every other leg and check to the line.
 """
 import argparse
 import json
@@ -75,7 +77,64 @@ def parse():
                         "runs the textureless step; the headline is albedo)")
     p.add_argument("--launcher-selftest", action="store_true",
                    help="CPU/gloo check of the N-rank launch only (no GPU work)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg and check (kernel "
+                        "timing and rooflines, host cost, replica check, the other backward, "
+                        "shading, module path, C5, C4 inference, CPU baseline), each unless "
+                        "its --no-* switch is given; without --full only the headline runs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (its loss and the state it "
+                        "left: parameters, density grid, rendered image) as DIR/<name>.npy")
+    args = p.parse_args()
+    if not args.full:
+        for leg in FULL_LEGS:
+            setattr(args, "no_" + leg, True)
+    return args
+
+
+# the legs beside the headline, each with a --no-<leg> switch; they run under --full only
+FULL_LEGS = ("cpu_baseline", "kernel_timing", "infer", "shading", "alt_backward", "module_path",
+             "c5", "traffic")
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: every array together
+DUMP_ARRAY_ELEMS = 2 << 20    # a larger array is dumped as a fixed seeded sample of this size
+
+
+def step_outputs(trainer, loss):
+    """What a caller of Trainer.train_iteration holds after a step: the loss it
+    returned and the state it updated in place (every parameter, the density
+    grid), and the image the native step rendered where that path ran."""
+    out = {"loss": loss}
+    for name, p in trainer.model.named_parameters():
+        out["param." + name] = p
+    if getattr(trainer.model, "cuda_ray", False):
+        out["density_grid"] = trainer.model.density_grid
+    g = next(iter(trainer._graphs.values()), None) if getattr(trainer, "_graphs", None) else None
+    image = getattr(getattr(g, "native", None), "image", None)
+    if image is not None:
+        out["pred_rgb"] = image
+    return out
+
+
+def dump_outputs(outputs, directory):
+    """Each array as float32 (float64 stays float64) in directory/<name>.npy.
+    An array above DUMP_ARRAY_ELEMS elements is written as the sample at
+    sorted indices drawn without replacement by numpy's default_rng(0), which
+    depends on the array's size alone, so two builds sample the same entries."""
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, t in outputs.items():
+        t = torch.as_tensor(t).detach()
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        a = t.contiguous().numpy()
+        if a.size > DUMP_ARRAY_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_ARRAY_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would exceed {DUMP_LIMIT_BYTES} bytes "
+                             f"at {name}")
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def env_options(model=None, trainer=None):
@@ -870,7 +929,7 @@ def main():
         trainer.pick_shading = (lambda k: (lambda: (k, 0.1)))(args.shade)
 
     def step():
-        trainer.train_iteration(data.collate([0]))
+        return trainer.train_iteration(data.collate([0]))
 
     for _ in range(args.warmup):
         step()
@@ -893,11 +952,15 @@ def main():
     # native step's graph holds the whole backward and, on one GPU, Adam)
     barrier()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(args.steps):
-        step()
+        loss = step()
     host_issue = time.perf_counter() - t0  # host done issuing (no sync inside the loop)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # now, before any later leg steps the trainer again
+        dump_outputs(step_outputs(trainer, loss), args.dump_outputs)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
@@ -908,22 +971,24 @@ def main():
     last = min(16, args.steps)
     rows = [(trainer.model.local_step - 1 - i) % 16 for i in range(last)]
     samples = float(trainer.model.step_counter[rows, 0].float().mean().item())
-    # the replicas after the timed region (every rank must hold the same
-    # model: DDP's contract), and each rank's own samples per step
-    identical, per_rank = replica_check(trainer, samples, world)
     kernels, timing = {}, None
+    if args.full:
+        # the replicas after the timed region (every rank must hold the same
+        # model: DDP's contract), and each rank's own samples per step
+        identical, per_rank = replica_check(trainer, samples, world)
     if not args.no_kernel_timing:
         kernels, timing = kernel_timing_pass(trainer, step, min(args.steps, 20))
-    # host work per step with no queue back-pressure: one step issued on an
-    # idle GPU (median of 16; the refresh step every 16 is the outlier)
-    issue = []
-    for _ in range(16):
+    if args.full:
+        # host work per step with no queue back-pressure: one step issued on an
+        # idle GPU (median of 16; the refresh step every 16 is the outlier)
+        issue = []
+        for _ in range(16):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            issue.append(time.perf_counter() - t1)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        issue.append(time.perf_counter() - t1)
-    torch.cuda.synchronize()
-    host_cost = float(np.median(issue))
+        host_cost = float(np.median(issue))
 
     rays_per_step = args.res * args.res
     steps_per_sec = args.steps * world / elapsed  # whole-job aggregate (every rank steps)
@@ -945,11 +1010,11 @@ def main():
                    "launch": "eager" if not trainer.graph_step else "hip-graph replay",
                    "mean_samples_per_step": round(samples, 1)},
         "steps_per_sec": round(steps_per_sec, 3),
-        "replicas_identical": identical,
-        "samples_per_step_per_rank": per_rank,
         "host_issue_ms_per_step": round(host_issue / args.steps * 1e3, 3),
-        "host_cost_ms_per_step": round(host_cost * 1e3, 3),
     }
+    if args.full:
+        result.update({"replicas_identical": identical, "samples_per_step_per_rank": per_rank,
+                       "host_cost_ms_per_step": round(host_cost * 1e3, 3)})
     g0 = next(iter(trainer._graphs.values()), None)
     result["config"]["grad_exchange"] = "none (one rank)"
     if g0 is not None:

@@ -242,6 +242,49 @@ def test_module_breakdown_counts_whole_steps(tmp_path):
     assert bench._module_breakdown([f], 5) is None
 
 
+def test_bench_dump_outputs_format(tmp_path, monkeypatch):
+    """bench.dump_outputs: one <name>.npy per array, float32 (float64 kept),
+    an array above the element cap written as the same seeded sample on every
+    call, and the byte limit over all arrays enforced."""
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [root, os.path.join(root, "single-stable-dreamfusion_amd")]
+    import bench
+    monkeypatch.setattr(bench, "DUMP_ARRAY_ELEMS", 1000)
+    big = torch.arange(5000, dtype=torch.int32).reshape(50, 100)  # exact in float32
+    outs = {"loss": torch.tensor(1.5, dtype=torch.float16), "w.0": big,
+            "d": torch.ones(3, dtype=torch.float64)}
+    bench.dump_outputs(outs, tmp_path / "a")
+    bench.dump_outputs(outs, tmp_path / "b")
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in outs}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["d.npy", "loss.npy", "w.0.npy"]
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == () and got["loss"] == 1.5
+    assert got["d"].dtype == np.float64
+    s = got["w.0"]
+    assert s.dtype == np.float32 and s.shape == (1000,)
+    assert len(np.unique(s)) == 1000 and (np.diff(s) > 0).all()  # distinct entries, in order
+    assert np.array_equal(s, np.load(tmp_path / "b" / "w.0.npy"))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(outs, tmp_path / "c")
+
+
+def test_bench_plain_run_has_no_other_leg(monkeypatch):
+    """Without --full every leg beside the headline is off, whatever --no-*
+    switches say; with --full each leg follows its own switch."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [root, os.path.join(root, "single-stable-dreamfusion_amd")]
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and not a.full and a.dump_outputs is None
+    assert all(getattr(a, "no_" + leg) for leg in bench.FULL_LEGS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-c5", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "x" and a.no_c5
+    assert not any(getattr(a, "no_" + leg) for leg in bench.FULL_LEGS if leg != "c5")
+
+
 def test_eval_background_side_stream_gating():
     """NeRFRenderer._background_async (the eval frame's background net beside
     the fused render) applies only to no-grad eval frames of one image on the

@@ -16,7 +16,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/s
     || { echo "smoke failed"; tail -20 $OUT/smoke.log; exit 2; }
 tail -1 $OUT/smoke.log
 fi
-timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 \
+timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 \
     || { echo "bench failed"; tail -30 $OUT/bench.log; exit 3; }
 grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
 python -c "import json; d=json.load(open('$OUT/bench.json')); print('ms/step', d['ms_per_step'], 'value', d['value'], 'roof', d.get('roofline',{}).get('frac'), 'infer', d.get('inference',{}).get('ms_per_frame'))"
