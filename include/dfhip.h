@@ -40,8 +40,15 @@ typedef void *dfhip_stream_t; /* hipStream_t */
 /* DFHIP_BF16: bfloat16 storage (the C5 bf16 option; no reference counterpart,
  * the reference dispatches f32 / f16 / f64 only). */
 enum dfhip_dtype { DFHIP_F32 = 0, DFHIP_F16 = 1, DFHIP_F64 = 2, DFHIP_BF16 = 3 };
-/* Shadings of the non-albedo train steps (nerf/network_grid.py:124-144). */
-enum dfhip_shading { DFHIP_SHADING_TEXTURELESS = 1, DFHIP_SHADING_LAMBERTIAN = 2 };
+/* Shadings (nerf/network_grid.py:124-144): the train steps take TEXTURELESS
+ * and LAMBERTIAN (albedo steps need no shading kernel), the shaded inference
+ * render those two and NORMAL (dfhip_render_rays_infer_shaded). */
+enum dfhip_shading {
+    DFHIP_SHADING_ALBEDO = 0,
+    DFHIP_SHADING_TEXTURELESS = 1,
+    DFHIP_SHADING_LAMBERTIAN = 2,
+    DFHIP_SHADING_NORMAL = 3
+};
 
 enum dfhip_status {
     DFHIP_OK = 0,
@@ -820,6 +827,43 @@ int dfhip_render_rays_infer_ordered(uint32_t N, const float *rays_o, const float
                                     float *image, uint32_t *work, const void *quads,
                                     const int32_t *order, uint32_t chunk_log2, uint32_t tile_w,
                                     uint64_t *prof, dfhip_stream_t stream);
+/* nerf/renderer.py:496-532 with network_grid.py:90-144 as the field — the
+ * shaded inference frames (the `textureless`, `lambertian` and `normal` views
+ * of test_step / test_gui, nerf/utils.py:414-418,616-671) in the same ONE
+ * persistent launch as dfhip_render_rays_infer_ordered, whose arguments,
+ * queue order, work and prof words it shares.  Every staged sample is
+ * evaluated at seven points, itself and clamp(x +- eps e_a, -bound, bound)
+ * (dfhip_shading_stencil's rows, same order), by the same gather + MLP; the
+ * colour follows dfhip_shading_forward's rounding points under fp16 autocast:
+ *   normal      = safe_normalize(-(0.5 (s+ - s-) / eps)), NaN -> 0       (f32)
+ *   lambertian  = f16(ratio + f16((1 - ratio) clamp(f16(normal @ f16(light)), 0)))
+ *   TEXTURELESS colour = lambertian on all channels                   (f16)
+ *   LAMBERTIAN  colour = f16(albedo * lambertian), albedo of the sample (f16)
+ *   NORMAL      colour = (normal + 1) / 2                             (f32)
+ * composited as composite_rays does (colours cast to f32).  Density, alpha,
+ * the T_thresh / max_steps / far retirement, depth and weights_sum are those
+ * of the albedo render.
+ * In:  as dfhip_render_rays_infer_ordered, then shading (a dfhip_shading code
+ *      other than ALBEDO, which the entry above serves), light [3] f32 (DEVICE;
+ *      the light direction, required for every shading), ratio (the ambient
+ *      ratio), eps (the stencil step, 1e-2 in the reference; > 0).
+ * Out: weights_sum [N], depth [N], image [N,3] f32, every ray written once.
+ * Errors (DFHIP_EINVAL): NULL light, an unknown or the ALBEDO shading code,
+ *      bound <= 0, eps <= 0, and those of the entry above.
+ * f16 tables only (a bf16 form does not exist). */
+int dfhip_render_rays_infer_shaded(uint32_t N, const float *rays_o, const float *rays_d,
+                                   const float *nears, const float *fars, const float *noises,
+                                   float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
+                                   uint32_t H, const uint8_t *grid, float T_thresh,
+                                   const void *table, const int32_t *offsets, uint32_t L,
+                                   float S, uint32_t base_res, uint32_t gridtype,
+                                   int align_corners, const float *w1, const float *b1,
+                                   const float *w2, const float *b2, const float *w3,
+                                   const float *b3, float *weights_sum, float *depth,
+                                   float *image, uint32_t *work, const void *quads,
+                                   const int32_t *order, uint32_t chunk_log2, uint32_t tile_w,
+                                   int shading, const float *light, float ratio, float eps,
+                                   uint64_t *prof, dfhip_stream_t stream);
 /* The queue order for dfhip_render_rays_infer_ordered: the chunks of
  * 2^chunk_log2 consecutive rays (rays_o / rays_d [N, 3] f32) by ascending
  * summed squared distance of their rays' lines from the scene centre (the

@@ -249,25 +249,11 @@ def render_ray_order(rays_o, rays_d, chunk_log2=6, cost=None, order=None, occ=No
     return order
 
 
-def render_rays_infer(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C, H,
-                      bitfield, T_thresh, table, offsets, S, base_res, gridtype, align_corners,
-                      weights, weights_sum, depth, image, work, quads=None, prof=None,
-                      order=None, chunk_log2=6, tile_w=0):
-    """Inference render of N rays in one launch (csrc/render.hip; reference
-    nerf/renderer.py:496-532).  rays_o/rays_d [N, 3] f32, nears/fars [N] f32,
-    noises [N] f32 or None, bitfield u8, table [rows, 2] f16, offsets int32.
-    Writes weights_sum [N], depth [N], image [N, 3] f32; work: [4] int32
-    scratch whose words 1, 2 hold the evaluated sample count afterwards;
-    quads: the table's corner quads ([rows, 4] int32, grid_quads) or None.
-    prof: [16 + 16 W] int64 device tensor receiving the kernel's per-wave phase
-    cycles and its wall-clock drain profile (dfhip_render_rays_infer_prof:
-    [6], [7] set to -1, the rest to 0 by the caller; tools only) or None.
-    order: [ceil(N / 2^chunk_log2)] int32 device permutation of the chunks
-    of 2^chunk_log2 consecutive rays (tile_w > 0: 8 x 8 pixel tiles of a
-    row-major image tile_w wide, as given to render_ray_order), the queue's
-    order (render_ray_order; taken in mirrored halves, see
-    dfhip_render_rays_infer_ordered; outputs are per ray, so identical), or
-    None for pixel order."""
+def _render_operands(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C, H,
+                     bitfield, T_thresh, table, offsets, S, base_res, gridtype, align_corners,
+                     weights, weights_sum, depth, image, work, quads, prof, order, chunk_log2):
+    """Operand checks of the fused render entries; returns the C arguments up
+    to `quads`."""
     n = rays_o.shape[0]
     for t, what in ((rays_o, "rays_o"), (rays_d, "rays_d"), (nears, "nears"), (fars, "fars"),
                     (weights_sum, "weights_sum"), (depth, "depth"), (image, "image")):
@@ -297,11 +283,6 @@ def render_rays_infer(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_
         checked(quads, "quads", "int")
         if tuple(quads.shape) != (table.shape[0], 4):
             raise RuntimeError("quads must be [rows, 4] int32 (grid_quads of the table)")
-    args = (n, ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(noises), float(bound),
-            float(dt_gamma), int(max_steps), int(C), int(H), ptr(bitfield), float(T_thresh),
-            ptr(table), ptr(offsets), offsets.shape[0] - 1, float(S), int(base_res),
-            int(gridtype), int(bool(align_corners)), *_weights(weights), ptr(weights_sum),
-            ptr(depth), ptr(image), ptr(work), ptr(quads))
     if prof is not None:
         checked(prof, "prof", "i64")
         if prof.numel() < 16 or prof.numel() < 16 + 16 * int(prof[10]):
@@ -310,9 +291,69 @@ def render_rays_infer(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_
         checked(order, "order", "int")
         if tuple(order.shape) != (-(-n // (1 << chunk_log2)),):
             raise RuntimeError("order must be [ceil(N / 2^chunk_log2)] int32")
+    return (n, ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(noises), float(bound),
+            float(dt_gamma), int(max_steps), int(C), int(H), ptr(bitfield), float(T_thresh),
+            ptr(table), ptr(offsets), offsets.shape[0] - 1, float(S), int(base_res),
+            int(gridtype), int(bool(align_corners)), *_weights(weights), ptr(weights_sum),
+            ptr(depth), ptr(image), ptr(work), ptr(quads))
+
+
+def render_rays_infer(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C, H,
+                      bitfield, T_thresh, table, offsets, S, base_res, gridtype, align_corners,
+                      weights, weights_sum, depth, image, work, quads=None, prof=None,
+                      order=None, chunk_log2=6, tile_w=0):
+    """Inference render of N rays in one launch (csrc/render.hip; reference
+    nerf/renderer.py:496-532).  rays_o/rays_d [N, 3] f32, nears/fars [N] f32,
+    noises [N] f32 or None, bitfield u8, table [rows, 2] f16, offsets int32.
+    Writes weights_sum [N], depth [N], image [N, 3] f32; work: [4] int32
+    scratch whose words 1, 2 hold the evaluated sample count afterwards;
+    quads: the table's corner quads ([rows, 4] int32, grid_quads) or None.
+    prof: [16 + 16 W] int64 device tensor receiving the kernel's per-wave phase
+    cycles and its wall-clock drain profile (dfhip_render_rays_infer_prof:
+    [6], [7] set to -1, the rest to 0 by the caller; tools only) or None.
+    order: [ceil(N / 2^chunk_log2)] int32 device permutation of the chunks
+    of 2^chunk_log2 consecutive rays (tile_w > 0: 8 x 8 pixel tiles of a
+    row-major image tile_w wide, as given to render_ray_order), the queue's
+    order (render_ray_order; taken in mirrored halves, see
+    dfhip_render_rays_infer_ordered; outputs are per ray, so identical), or
+    None for pixel order."""
+    args = _render_operands(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C,
+                            H, bitfield, T_thresh, table, offsets, S, base_res, gridtype,
+                            align_corners, weights, weights_sum, depth, image, work, quads, prof,
+                            order, chunk_log2)
+    if order is not None:
         call("dfhip_render_rays_infer_ordered", *args, ptr(order), int(chunk_log2), int(tile_w),
              ptr(prof), stream())
     elif prof is None:
         call("dfhip_render_rays_infer", *args, stream())
     else:
         call("dfhip_render_rays_infer_prof", *args, ptr(prof), stream())
+
+
+SHADINGS = {"albedo": 0, "textureless": 1, "lambertian": 2, "normal": 3}  # dfhip_shading
+
+
+def render_rays_infer_shaded(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C,
+                             H, bitfield, T_thresh, table, offsets, S, base_res, gridtype,
+                             align_corners, weights, weights_sum, depth, image, work, shading,
+                             light, ratio, eps=1e-2, quads=None, prof=None, order=None,
+                             chunk_log2=6, tile_w=0):
+    """render_rays_infer for the shaded frames (dfhip_render_rays_infer_shaded;
+    reference network_grid.py:90-144 as the loop's field): shading
+    "textureless" / "lambertian" / "normal" (or its dfhip_shading code), light
+    [3] f32 device tensor (the light direction), ratio the ambient ratio, eps
+    the finite-difference step.  The other operands, their checks and the
+    outputs are render_rays_infer's."""
+    args = _render_operands(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C,
+                            H, bitfield, T_thresh, table, offsets, S, base_res, gridtype,
+                            align_corners, weights, weights_sum, depth, image, work, quads, prof,
+                            order, chunk_log2)
+    code = SHADINGS.get(shading, shading) if isinstance(shading, str) else shading
+    if isinstance(code, str):
+        raise RuntimeError(f"unknown shading {shading!r}")
+    if light is not None:
+        _f32(light, "light")
+        if light.numel() != 3:
+            raise RuntimeError("light must hold 3 float32 values")
+    call("dfhip_render_rays_infer_shaded", *args, ptr(order), int(chunk_log2), int(tile_w),
+         int(code), ptr(light), float(ratio), float(eps), ptr(prof), stream())

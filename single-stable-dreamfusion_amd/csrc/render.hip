@@ -53,9 +53,20 @@
 //    deltas / sigma / rgb intermediates never touch HBM.  Every ray id
 //    taken is finished before its wave exits, so each output is written
 //    exactly once (no zero-fill).
+//
+// Shaded frames (dfhip_render_rays_infer_shaded: the textureless, lambertian
+// and normal views, network_grid.py:90-144 as the loop's field) are the same
+// kernel instantiated on the shading: the field phase evaluates each staged
+// sample at its seven finite-difference stencil points (k_stencil's rows)
+// and forms the colour with shade_common.h's fd_normal / lambert, the train
+// step's rounding points; everything else is shared, so density, depth and
+// weights_sum are the albedo frame's.  Bit-identical to the loop of
+// march_rays -> shading_stencil -> grid field (7 M rows) -> shading_forward
+// -> composite_rays (tests/test_gpu_render_shaded.py).
 #include "march_common.h"
 #include <type_traits>
 #include "field_common.h"
+#include "shade_common.h"
 
 namespace dfhip {
 namespace rd {
@@ -106,6 +117,22 @@ struct Stage {
     float tc[kSlots];  // rays_t after the sample (the depth weight's t)
 };
 
+// Shading of the composited colour (the dfhip_shading codes; 0 = albedo).
+constexpr int kAlbedo = 0, kTextureless = DFHIP_SHADING_TEXTURELESS,
+              kLambertian = DFHIP_SHADING_LAMBERTIAN, kNormal = DFHIP_SHADING_NORMAL;
+// The normal view composites f32 colours (sigma and two channels in the slot's
+// pos words, the third here); the other modes pack f16 colours into pos.
+template <int MODE> struct StageT : Stage {};
+template <> struct StageT<kNormal> : Stage {
+    float cz[kSlots];
+};
+// light: DEVICE f32 [3]; omr = 1 - ratio (rounded as dfhip_shading_forward's);
+// eps: the finite-difference step.  Unused by the albedo mode.
+struct ShadeArgs {
+    const float *light;
+    float ratio, omr, eps;
+};
+
 // Ray j of queue chunk ch: 2^cl consecutive ray ids, or with tile_w (the
 // width of a row-major image; cl = 6) pixel (j / 8, j % 8) of the image's
 // 8 x 8 tile ch (tiles row-major).  A tile's rays stay closer in 3-D than a
@@ -136,8 +163,17 @@ __device__ __forceinline__ float hi_h(uint32_t v) {
     return (float)h;
 }
 
+// Unused by the albedo mode, whose kernel takes no shading arguments.
+struct NoShade {};
+template <int MODE> struct ShadeOf { typedef ShadeArgs type; };
+template <> struct ShadeOf<kAlbedo> { typedef NoShade type; };
+
+// The persistent render kernel, instantiated per shading MODE (a template
+// parameter, no run-time branch on it): kAlbedo is the albedo frame's kernel,
+// the other three evaluate seven field points per sample.
 // 3 waves per SIMD (<= 170 VGPRs): the register count sits at that
 // boundary, and one more wave per SIMD is worth ~6 % of the frame
+template <int MODE>
 __global__ __launch_bounds__(256, 3) void k_render_infer(
     uint32_t N, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
     const float *__restrict__ nears, const float *__restrict__ fars,
@@ -148,17 +184,23 @@ __global__ __launch_bounds__(256, 3) void k_render_infer(
     const float *b3, float *__restrict__ weights_sum, float *__restrict__ depth,
     float *__restrict__ image, uint32_t *__restrict__ work,
     const fm::u32x4 *__restrict__ quads, uint64_t *prof, const int32_t *__restrict__ order,
-    uint32_t chunk_log2, uint32_t tile_w) {
+    uint32_t chunk_log2, uint32_t tile_w, typename ShadeOf<MODE>::type sh) {
     __shared__ fm::Weights W;
     __shared__ fm::LevelK LK[fm::kLevels];
-    __shared__ Stage stages[kWaves];
+    __shared__ StageT<MODE> stages[kWaves];
     const bool align = align_corners != 0;
     fm::load_weights<true>(W, nullptr, w1, b1, w2, b2, w3, b3);
     fm::stage_levels(LK, offsets, lv, gridtype, align);
     __syncthreads();
-    Stage &S = stages[threadIdx.x >> 6];
+    StageT<MODE> &S = stages[threadIdx.x >> 6];
     const int lane = threadIdx.x & 63, c = lane & 15, h = lane >> 4;
     const float inv_extent = 1.0f / (2.0f * k.bound);
+    // the light as autocast holds it, rounded once per kernel (k_shade_fwd)
+    float l16[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (MODE == kTextureless || MODE == kLambertian) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) l16[d] = shd::rnd<half_t>(sh.light[d]);
+    }
     // queue positions: N, or whole chunks of the order
     const uint32_t nchunks = ceil_div(N, 1u << chunk_log2);
     const uint32_t Nq = order ? nchunks << chunk_log2 : N;
@@ -321,6 +363,110 @@ __global__ __launch_bounds__(256, 3) void k_render_infer(
         if (prof) pc[5] += tiles;
         // kTPP tiles per pass: their table gathers are issued before any MLP
         // waits on them (more loads in flight per lane)
+        if constexpr (MODE != kAlbedo) {
+            // Shaded: every staged sample is evaluated at seven points, itself
+            // (p = 0) and the clamped stencil points p = 1 + 2 a (+eps e_a),
+            // 2 + 2 a (-eps e_a) of k_stencil, by the same gather + MLP; kTPP
+            // tiles per pass as below (point p of each tile gathered before
+            // either MLP).  The lane of group 0 that owns sample c keeps the
+            // seven densities, forms the normal and the lambertian term after
+            // the last pass and hands the latter to groups 1..3 (which kept
+            // the centre point's albedo) by a lane read.
+            for (uint32_t tile = 0; tile < tiles; tile += kTPP) {
+                float sig[kTPP][7];
+                bool valid[kTPP];
+                half_t alb[kTPP];
+#pragma unroll
+                for (int u = 0; u < kTPP; ++u) {
+                    valid[u] = (tile + u) * 16 + c < total;
+                    alb[u] = (half_t)0.0f;
+#pragma unroll
+                    for (int p = 0; p < 7; ++p) sig[u][p] = 0.0f;
+                }
+                for (int p = 0; p < 7; ++p) {
+                    const int a = (p - 1) >> 1;
+                    const float off = ((p - 1) & 1) ? -sh.eps : sh.eps;
+                    // the positions stay in LDS until the tile's last pass: read
+                    // again per pass (registers), the density blob taken here
+                    float x01[kTPP][3], blob[kTPP];
+                    fm::half8 xb[kTPP];
+#pragma unroll
+                    for (int u = 0; u < kTPP; ++u) {
+                        const uint32_t s = (tile + u) * 16 + c;
+                        float xp[3];
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) {
+                            const float x = valid[u] ? S.pos[3 * s + d] : 0.0f;
+                            // x + tensor([[eps, 0, 0]]) then clamp(-bound, bound)
+                            const float v =
+                                fminf(fmaxf(x + (d == a ? off : 0.0f), -k.bound), k.bound);
+                            xp[d] = p ? v : x;
+                            x01[u][d] = valid[u] ? (xp[d] + k.bound) * inv_extent : -1.0f;
+                        }
+                        blob[u] = fm::gaussian(xp);
+                    }
+#pragma unroll
+                    for (int u = 0; u < kTPP; ++u)
+                        xb[u] = quads ? fm::grid_features<half_t, true>(table, LK, align, x01[u],
+                                                                        h, quads)
+                                      : fm::grid_features(table, LK, align, x01[u], h);
+#pragma unroll
+                    for (int u = 0; u < kTPP; ++u) {
+                        if (u > 0 && tile + u >= tiles) break;  // uniform
+                        fm::Fwd F;
+                        fm::forward_tile(W, xb[u], c, h, F);
+                        // k_field_fwd_fused's heads: the f32 density of point p
+                        // (group 0), the f16 albedo of the centre point (1..3)
+                        const float v = (float)(half_t)F.o[0];
+                        if (h == 0) {
+                            const float sg = expf(v + blob[u]);
+#pragma unroll
+                            for (int q = 0; q < 7; ++q) sig[u][q] = p == q ? sg : sig[u][q];
+                        } else if (MODE == kLambertian && p == 0) {
+                            alb[u] = (half_t)(1.0f / (1.0f + expf(-v)));
+                        }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kTPP; ++u) {
+                    if (u > 0 && tile + u >= tiles) break;  // uniform
+                    const uint32_t s = (tile + u) * 16 + c;
+                    const shd::Normal nm = shd::fd_normal(sig[u], 0u, sh.eps);
+                    if constexpr (MODE == kNormal) {
+                        // (normal + 1) / 2 in f32 (network_grid.py:140)
+                        if (valid[u] && h == 0) {
+                            S.pos[3 * s] = sig[u][0];
+                            S.pos[3 * s + 1] = (nm.n[0] + 1.0f) * 0.5f;
+                            S.pos[3 * s + 2] = (nm.n[1] + 1.0f) * 0.5f;
+                            S.cz[s] = (nm.n[2] + 1.0f) * 0.5f;
+                        }
+                    } else {
+                        const shd::Shade sd = shd::lambert<half_t>(nm.n, l16, sh.ratio, sh.omr);
+                        if constexpr (MODE == kTextureless) {
+                            if (valid[u] && h == 0) {
+                                const half_t l = (half_t)sd.lam16;
+                                S.pos[3 * s] = sig[u][0];
+                                S.pos[3 * s + 1] = __uint_as_float(pack_h2(l, l));
+                                S.pos[3 * s + 2] = __uint_as_float(pack_h2(l, (half_t)0.0f));
+                            }
+                        } else {
+                            // albedo * lambertian as f16 values, channel h - 1
+                            const float lam = __shfl(sd.lam16, c);
+                            const half_t col = (half_t)shd::rnd<half_t>((float)alb[u] * lam);
+                            if (valid[u]) {
+                                if (h == 0)
+                                    S.pos[3 * s] = sig[u][0];
+                                else if (h == 3)
+                                    S.pos[3 * s + 2] =
+                                        __uint_as_float(pack_h2(col, (half_t)0.0f));
+                                else
+                                    reinterpret_cast<half_t *>(S.pos + 3 * s + 1)[h - 1] = col;
+                            }
+                        }
+                    }
+                }
+            }
+        } else
         for (uint32_t tile = 0; tile < tiles; tile += kTPP) {
             float x[kTPP][3], x01[kTPP][3];
             bool valid[kTPP];
@@ -383,9 +529,15 @@ __global__ __launch_bounds__(256, 3) void k_render_infer(
                 const float w = alpha * T;
                 ws += w;
                 dp = fmaf(w, S.tc[slot], dp);
-                cr = fmaf(w, lo_h(rg), cr);
-                cg = fmaf(w, hi_h(rg), cg);
-                cb = fmaf(w, lo_h(bz), cb);
+                if constexpr (MODE == kNormal) {  // f32 colours
+                    cr = fmaf(w, __uint_as_float(rg), cr);
+                    cg = fmaf(w, __uint_as_float(bz), cg);
+                    cb = fmaf(w, S.cz[slot], cb);
+                } else {
+                    cr = fmaf(w, lo_h(rg), cr);
+                    cg = fmaf(w, hi_h(rg), cg);
+                    cb = fmaf(w, lo_h(bz), cb);
+                }
                 ++taken;
                 ++samples;
                 if (T < T_thresh || taken >= max_samples) finished = true;
@@ -456,6 +608,7 @@ __global__ __launch_bounds__(256, 3) void k_render_infer(
 
 using namespace dfhip;
 
+// shading: a dfhip_shading code; sh is read by the non-albedo ones
 static int render_infer(
     uint32_t N, const float *rays_o, const float *rays_d, const float *nears, const float *fars,
     const float *noises, float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
@@ -464,8 +617,9 @@ static int render_infer(
     const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
     const float *b3, float *weights_sum, float *depth, float *image, uint32_t *work,
     const void *quads, uint64_t *prof, const int32_t *order, uint32_t chunk_log2,
-    uint32_t tile_w, dfhip_stream_t stream) {
-    const char *name = "render_rays_infer";
+    uint32_t tile_w, dfhip_stream_t stream, int shading = rd::kAlbedo,
+    const rd::ShadeArgs &sh = rd::ShadeArgs{},
+    const char *name = "render_rays_infer") {
     if (order && tile_w && (chunk_log2 != 6 || tile_w % 8 || N % (8 * tile_w))) {
         set_error("%s: tile chunks need chunk_log2 6, tile_w a multiple of 8 and N of 8 tile_w "
                   "(got chunk_log2 %u, tile_w %u, N %u)", name, chunk_log2, tile_w, N);
@@ -498,15 +652,20 @@ static int render_infer(
     const ge::Levels lv = ge::make_levels(L, S, base_res);
     // persistent waves: as many workgroups as are co-resident on the chip
     // (occupancy query, cached per device); the queue balances the rays
-    const uint32_t resident =
-        resident_blocks((const void *)rd::k_render_infer, 64 * rd::kWaves, 2);
-    const uint32_t want = ceil_div(N, 64u * rd::kWaves);
-    const uint32_t blocks = want < resident ? want : resident;
-    rd::k_render_infer<<<blocks, 64 * rd::kWaves, 0, s>>>(
-        N, rays_o, rays_d, nears, fars, noises, k, grid, max_steps, T_thresh,
-        (const half_t *)table, offsets, lv, gridtype, align_corners, w1, b1, w2, b2, w3, b3,
-        weights_sum, depth, image, work, (const fm::u32x4 *)quads, prof, order, chunk_log2,
-        tile_w);
+    auto launch = [&](auto kernel, auto shade) {
+        const uint32_t resident = resident_blocks((const void *)kernel, 64 * rd::kWaves, 2);
+        const uint32_t want = ceil_div(N, 64u * rd::kWaves);
+        const uint32_t blocks = want < resident ? want : resident;
+        kernel<<<blocks, 64 * rd::kWaves, 0, s>>>(
+            N, rays_o, rays_d, nears, fars, noises, k, grid, max_steps, T_thresh,
+            (const half_t *)table, offsets, lv, gridtype, align_corners, w1, b1, w2, b2, w3, b3,
+            weights_sum, depth, image, work, (const fm::u32x4 *)quads, prof, order, chunk_log2,
+            tile_w, shade);
+    };
+    if (shading == rd::kTextureless) launch(rd::k_render_infer<rd::kTextureless>, sh);
+    else if (shading == rd::kLambertian) launch(rd::k_render_infer<rd::kLambertian>, sh);
+    else if (shading == rd::kNormal) launch(rd::k_render_infer<rd::kNormal>, sh);
+    else launch(rd::k_render_infer<rd::kAlbedo>, rd::NoShade{});
     return check_launch(name);
 }
 
@@ -551,6 +710,47 @@ extern "C" int dfhip_render_rays_infer_ordered(
                         grid, T_thresh, table, offsets, L, S, base_res, gridtype, align_corners,
                         w1, b1, w2, b2, w3, b3, weights_sum, depth, image, work, quads, prof,
                         order, chunk_log2, tile_w, stream);
+}
+
+// The shaded frames: argument checks of the shading, then the launcher above.
+extern "C" int dfhip_render_rays_infer_shaded(
+    uint32_t N, const float *rays_o, const float *rays_d, const float *nears, const float *fars,
+    const float *noises, float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
+    uint32_t H, const uint8_t *grid, float T_thresh, const void *table, const int32_t *offsets,
+    uint32_t L, float S, uint32_t base_res, uint32_t gridtype, int align_corners,
+    const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+    const float *b3, float *weights_sum, float *depth, float *image, uint32_t *work,
+    const void *quads, const int32_t *order, uint32_t chunk_log2, uint32_t tile_w, int shading,
+    const float *light, float ratio, float eps, uint64_t *prof, dfhip_stream_t stream) {
+    const char *name = "render_rays_infer_shaded";
+    if (shading == DFHIP_SHADING_ALBEDO) {
+        set_error("%s: the albedo shading is dfhip_render_rays_infer_ordered's", name);
+        return DFHIP_EINVAL;
+    }
+    if (shading != DFHIP_SHADING_TEXTURELESS && shading != DFHIP_SHADING_LAMBERTIAN &&
+        shading != DFHIP_SHADING_NORMAL) {
+        set_error("%s: shading must be DFHIP_SHADING_TEXTURELESS, _LAMBERTIAN or _NORMAL "
+                  "(got %d)", name, shading);
+        return DFHIP_EINVAL;
+    }
+    if (!light) {
+        set_error("%s: light is NULL (a DEVICE f32 [3] direction is required)", name);
+        return DFHIP_EINVAL;
+    }
+    if (!(bound > 0.0f)) {
+        set_error("%s: bound must be > 0 (got %g)", name, (double)bound);
+        return DFHIP_EINVAL;
+    }
+    if (!(eps > 0.0f)) {
+        set_error("%s: eps must be > 0 (got %g)", name, (double)eps);
+        return DFHIP_EINVAL;
+    }
+    // 1 - ratio as dfhip_shading_forward rounds it
+    const rd::ShadeArgs sh{light, ratio, (float)(1.0 - (double)ratio), eps};
+    return render_infer(N, rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C, H,
+                        grid, T_thresh, table, offsets, L, S, base_res, gridtype, align_corners,
+                        w1, b1, w2, b2, w3, b3, weights_sum, depth, image, work, quads, prof,
+                        order, chunk_log2, tile_w, stream, shading, sh, name);
 }
 
 // ---------------------------------------------------------------- queue order

@@ -125,9 +125,18 @@ class NeRFNetwork(NeRFRenderer):
         return {"sigma": sigma, "albedo": albedo}
 
     def native_infer_field(self, shading, x):
-        if shading != "albedo" or not self.fused_field:
+        """(encoder, sigma_net layers) when the fused inference renderer serves
+        `shading`: albedo, and under fp16 autocast textureless, lambertian and
+        normal (csrc/render.hip evaluates the finite-difference stencil in the
+        persistent launch).  The shaded kernels round at the f16 points only:
+        under bf16 autocast shaded frames keep the host loop (_infer_loop)."""
+        if shading not in ("albedo", "textureless", "lambertian", "normal"):
+            return None
+        if not self.fused_field:
             return None
         if not _field.eligible(self.encoder, self.sigma_net.net, x):
+            return None
+        if shading != "albedo" and torch.get_autocast_dtype("cuda") != torch.float16:
             return None
         return self.encoder, list(self.sigma_net.net)
 

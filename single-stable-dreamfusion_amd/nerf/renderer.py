@@ -309,7 +309,8 @@ class NeRFRenderer(nn.Module):
                 bg = self._background_async(rays_d, nears, fars, prefix, bg_color)
                 weights_sum, depth, image = self._infer_fused(
                     rays_o, rays_d, nears, fars, field, perturb, dt_gamma, max_steps, T_thresh,
-                    render_stream=bg[2] if bg else None)
+                    render_stream=bg[2] if bg else None, shading=shading, light_d=light_d,
+                    ambient_ratio=ambient_ratio)
                 if bg:  # the background net ran beside the render
                     torch.cuda.current_stream().wait_event(bg[1])
                     bg[0].record_stream(torch.cuda.current_stream())
@@ -412,10 +413,15 @@ class NeRFRenderer(nn.Module):
         self.__dict__.pop("_infer_operands", None)
 
     def _infer_fused(self, rays_o, rays_d, nears, fars, field, perturb, dt_gamma, max_steps,
-                     T_thresh, render_stream=None):
+                     T_thresh, render_stream=None, shading="albedo", light_d=None,
+                     ambient_ratio=1.0):
         """The inference loop below as ONE persistent launch (csrc/render.hip):
         march, grid field and compositing per ray with a device work queue, no
-        host sync and no per-sample intermediates in HBM."""
+        host sync and no per-sample intermediates in HBM.  A shading other
+        than albedo (textureless / lambertian / normal, network_grid.py:90-144)
+        takes the shaded kernel, which evaluates each sample's
+        finite-difference stencil in the same launch; light_d: [3] device
+        tensor, ambient_ratio: the ambient share."""
         import _fieldmlp
         import numpy as np
         encoder, layers = field
@@ -480,22 +486,35 @@ class NeRFRenderer(nn.Module):
                                                    tile_w=tile_w)
         operands = (rays_o.float().contiguous(), rays_d.float().contiguous(),
                     nears.float().contiguous(), fars.float().contiguous())
+        light = None
+        if shading != "albedo":
+            if light_d is None:
+                raise RuntimeError(f"the {shading} shading needs a light direction")
+            # a device tensor stays one: no host read of the light
+            light = torch.as_tensor(light_d).detach().to(dev).reshape(3).float().contiguous()
         main = torch.cuda.current_stream()
         rs = render_stream if render_stream is not None else main
         if rs is not main:  # the render on its own stream (beside a side-stream job)
             rs.wait_stream(main)
-        with torch.cuda.stream(rs), _dfhip.timed("render_rays_infer", nbytes):
-            _fieldmlp.render_rays_infer(
-                *operands, noises, self.bound,
+        args = (*operands, noises, self.bound,
                 dt_gamma, max_steps, self.cascade, self.grid_size, self.density_bitfield,
                 T_thresh, table, encoder.offsets, float(np.log2(encoder.per_level_scale)),
                 int(encoder.base_resolution), encoder.gridtype_id, bool(encoder.align_corners),
-                weights, weights_sum, depth, image, work, quads, order=order, chunk_log2=cl,
-                tile_w=tile_w)
+                weights, weights_sum, depth, image, work)
+        if shading == "albedo":
+            with torch.cuda.stream(rs), _dfhip.timed("render_rays_infer", nbytes):
+                _fieldmlp.render_rays_infer(*args, quads, order=order, chunk_log2=cl,
+                                            tile_w=tile_w)
+        else:
+            # the same launch with seven field points per sample (csrc/render.hip)
+            with torch.cuda.stream(rs), _dfhip.timed("render_rays_infer_shaded", nbytes + 12):
+                _fieldmlp.render_rays_infer_shaded(*args, shading, light, float(ambient_ratio),
+                                                   1e-2, quads=quads, order=order,
+                                                   chunk_log2=cl, tile_w=tile_w)
         if rs is not main:
             main.wait_stream(rs)
             for t in (*operands, weights_sum, depth, image, work, order, noises, table, quads,
-                      *weights):
+                      light, *weights):
                 if torch.is_tensor(t):
                     t.record_stream(rs)
         self.last_infer_work = work  # work[1] (+ 2^32 work[2]) = samples evaluated

@@ -118,6 +118,15 @@ def get_rays_host_pose(poses, intrinsics, H, W, device, out=None):
     return {"rays_o": rays_o, "rays_d": rays_d}
 
 
+def light_from_angles(theta_phi):
+    """The GUI's light sliders (theta, phi in degrees) as a unit direction
+    (reference utils.py:628-633): (sin t sin p, cos t, sin t cos p), float32
+    numpy [3]; theta is measured from +y, phi around it from +z."""
+    t, p = (float(v) for v in np.deg2rad(np.asarray(theta_phi, dtype=np.float64)))
+    return np.array([math.sin(t) * math.sin(p), math.cos(t), math.sin(t) * math.cos(p)],
+                    dtype=np.float32)
+
+
 def seed_everything(seed):
     """utils.py seed_everything, minus PYTHONHASHSEED: the hash seed is fixed
     when the interpreter starts, so setting it here only reaches child
@@ -225,6 +234,23 @@ class _EMA:
     def update(self):
         for s, p in zip(self.shadow, self.params):
             s.mul_(self.decay).add_(p.detach(), alpha=1 - self.decay)
+
+    # torch_ema's store / copy_to / restore: evaluate with the averaged
+    # parameters, then put the trained ones back
+    @torch.no_grad()
+    def store(self):
+        self.saved = [p.detach().clone() for p in self.params]
+
+    @torch.no_grad()
+    def copy_to(self):
+        for s, p in zip(self.shadow, self.params):
+            p.copy_(s)
+
+    @torch.no_grad()
+    def restore(self):
+        for v, p in zip(self.saved, self.params):
+            p.copy_(v)
+        self.saved = None
 
     def state_dict(self):
         return {"decay": self.decay, "shadow": self.shadow}
@@ -639,17 +665,86 @@ class Trainer(object):
         self.log(f"[INFO] training takes {(time.time() - start) / 60:.4f} minutes.")
 
     # ------------------------------------------------------------ eval
+    @staticmethod
+    def _view_shading(data):
+        """(shading, ambient_ratio, light_d) of an eval batch (utils.py:414-416,
+        447-449): the batch's keys, else the albedo view."""
+        return (data.get("shading", "albedo"), data.get("ambient_ratio", 1.0),
+                data.get("light_d", None))
+
     @torch.no_grad()
-    def test_step(self, data, bg_color=None, perturb=False):
+    def eval_step(self, data):
+        """utils.py:406-433: the view of `data` (its shading / ambient_ratio /
+        light_d keys when present) and the entropy regulariser of its
+        weights_sum.  Returns (pred_rgb [B,H,W,3], pred_depth [B,H,W], loss)."""
         rays_o, rays_d = data["rays_o"], data["rays_d"]
         B, N = rays_o.shape[:2]
         H, W = data["H"], data["W"]
+        shading, ambient_ratio, light_d = self._view_shading(data)
+        if H * W == N:
+            self.model.infer_tile_w = W
+        out = self.model.render(rays_o, rays_d, staged=True, perturb=False, bg_color=None,
+                                light_d=light_d, ambient_ratio=ambient_ratio, shading=shading,
+                                force_all_rays=True, **vars(self.opt))
+        pred_ws = out["weights_sum"].reshape(B, H, W)
+        a = pred_ws.clamp(1e-5, 1 - 1e-5)
+        entropy = (-a * torch.log2(a) - (1 - a) * torch.log2(1 - a)).mean()
+        loss = self.opt.lambda_entropy * entropy
+        return out["image"].reshape(B, H, W, 3), out["depth"].reshape(B, H, W), loss
+
+    @torch.no_grad()
+    def test_step(self, data, bg_color=None, perturb=False):
+        """utils.py:435-458: the view of `data`; its shading, ambient_ratio and
+        light_d keys select a relit / textureless / normal view (absent: the
+        albedo view)."""
+        rays_o, rays_d = data["rays_o"], data["rays_d"]
+        B, N = rays_o.shape[:2]
+        H, W = data["H"], data["W"]
+        shading, ambient_ratio, light_d = self._view_shading(data)
         if H * W == N:  # row-major images: the fused renderer's queue takes 8 x 8 tiles
             self.model.infer_tile_w = W
-        out = self.model.render(rays_o, rays_d, staged=True, perturb=perturb, light_d=None,
-                                ambient_ratio=1.0, shading="albedo", force_all_rays=True,
-                                bg_color=bg_color, **vars(self.opt))
+        out = self.model.render(rays_o, rays_d, staged=True, perturb=perturb, light_d=light_d,
+                                ambient_ratio=ambient_ratio, shading=shading,
+                                force_all_rays=True, bg_color=bg_color, **vars(self.opt))
         return out["image"].reshape(B, H, W, 3), out["depth"].reshape(B, H, W)
+
+    def test_gui(self, pose, intrinsics, W, H, bg_color=None, spp=1, downscale=1, light_d=None,
+                 ambient_ratio=1.0, shading="albedo"):
+        """One GUI frame (utils.py:616-671): pose [4, 4] cam2world (numpy),
+        intrinsics (fx, fy, cx, cy) at W x H, rendered at downscale and resized
+        back by nearest neighbour; light_d = (theta, phi) in degrees (None: a
+        random light, as render() draws it); the EMA parameters when an EMA is
+        kept.  Returns {'image' [H, W, 3], 'depth' [H, W]} numpy f32."""
+        rH, rW = int(H * downscale), int(W * downscale)
+        intrinsics = np.asarray(intrinsics, dtype=np.float64) * downscale
+        pose = torch.from_numpy(np.asarray(pose, dtype=np.float32)).unsqueeze(0).to(self.device)
+        rays = get_rays(pose, intrinsics, rH, rW, -1)
+        data = {"rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "H": rH, "W": rW,
+                "ambient_ratio": ambient_ratio, "shading": shading}
+        if light_d is not None:
+            data["light_d"] = torch.from_numpy(light_from_angles(light_d)).to(self.device)
+        self.model.eval()
+        # the parameters change under the renderer's cached launch operands
+        stale = getattr(self.model, "invalidate_infer_operands", lambda: None)
+        if self.ema is not None:
+            self.ema.store()
+            self.ema.copy_to()
+            stale()
+        try:
+            with torch.autocast("cuda", enabled=self.amp, dtype=self.amp_dtype):
+                # spp is the reference's perturb argument here (utils.py:655)
+                preds, preds_depth = self.test_step(data, bg_color=bg_color, perturb=spp)
+        finally:
+            if self.ema is not None:
+                self.ema.restore()
+                stale()
+        if downscale != 1:
+            preds = F.interpolate(preds.permute(0, 3, 1, 2), size=(H, W),
+                                  mode="nearest").permute(0, 2, 3, 1).contiguous()
+            preds_depth = F.interpolate(preds_depth.unsqueeze(1), size=(H, W),
+                                        mode="nearest").squeeze(1)
+        return {"image": preds[0].float().cpu().numpy(),
+                "depth": preds_depth[0].float().cpu().numpy()}
 
     # ------------------------------------------------------------ checkpoints
     def save_mesh(self, save_path=None, resolution=128):

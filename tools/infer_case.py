@@ -1,6 +1,8 @@
 """C4 fused inference renderer (csrc/render.hip k_render_infer) on the bench's
 800x800 scene (tools for timing studies / PMC passes):
-    python tools/infer_case.py [--reps 10] [--res 800]"""
+    python tools/infer_case.py [--reps 10] [--res 800]
+Shaded frames (textureless / lambertian / normal views), fused or the host loop:
+    python tools/infer_case.py --shading lambertian [--ambient 0.1] [--loop]"""
 import argparse
 import sys
 from pathlib import Path
@@ -26,6 +28,13 @@ def main():
                     help="queue order: 0 pixel, 1 line distance, 2 occupied cells (renderer.infer_order)")
     ap.add_argument("--dump", default="", help="save the per-wave records (.npy; last row: prof[:16])")
     ap.add_argument("--sphere", action="store_true", help="analytic sphere occupancy (R1)")
+    ap.add_argument("--shading", default="albedo",
+                    choices=["albedo", "textureless", "lambertian", "normal"],
+                    help="shading of the frame (renderer.render's)")
+    ap.add_argument("--ambient", type=float, default=0.1,
+                    help="ambient ratio of a shaded frame (albedo frames: 1.0)")
+    ap.add_argument("--loop", action="store_true",
+                    help="the march / field / composite host loop (renderer.native_infer = False)")
     args = ap.parse_args()
     import main as m
     from nerf.network_grid import NeRFNetwork
@@ -43,16 +52,22 @@ def main():
         import bench
         bench.sphere_occupancy_(model)
     model.eval()
-    model.native_infer = True
+    model.native_infer = not args.loop
     model.infer_tile_w = 0 if args.strips else args.res
     model.infer_overlap_bg = not args.serial_bg
     model.infer_order = args.order
     data = NeRFDataset(opt, device=dev, type="test", H=args.res, W=args.res, size=8).collate([1])
 
+    shaded = args.shading != "albedo"
+    # a fixed light (the GUI's default sliders, theta 60 phi 0), on the device
+    from nerf.utils import light_from_angles
+    light = torch.from_numpy(light_from_angles((60.0, 0.0))).to(dev) if shaded else None
+    ambient = args.ambient if shaded else 1.0
+
     def frame():
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
             return model.render(data["rays_o"], data["rays_d"], staged=True, perturb=False,
-                                light_d=None, ambient_ratio=1.0, shading="albedo",
+                                light_d=light, ambient_ratio=ambient, shading=args.shading,
                                 force_all_rays=True, bg_color=None, **vars(opt))
     for _ in range(3):
         out = frame()
@@ -65,21 +80,30 @@ def main():
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / args.reps
     img = out["image"].float()
-    print(f"res={args.res} ms_per_frame={ms:.3f} image_mean={float(img.mean()):.6f} "
+    work = getattr(model, "last_infer_work", None) if model.native_infer else None
+    samples = "-"
+    if work is not None:  # the fused launch's composited samples
+        w = work.cpu().numpy().view("uint32")
+        samples = int(w[1]) + (int(w[2]) << 32)
+    print(f"res={args.res} shading={args.shading} path={'loop' if args.loop else 'fused'} "
+          f"ms_per_frame={ms:.3f} samples={samples} image_mean={float(img.mean()):.6f} "
           f"ws_mean={float(out['weights_sum'].float().mean()):.6f}", flush=True)
-    if args.profile:
+    if args.profile and args.loop:
+        print("--profile needs the fused path (no --loop)", flush=True)
+    elif args.profile:
         import functools
         import _fieldmlp
         W = 8192  # per-wave records
         prof = torch.zeros(16 + 16 * W, dtype=torch.int64, device=dev)
         prof[6] = prof[7] = -1  # UINT64_MAX (atomicMin slots)
         prof[10] = W
-        plain = _fieldmlp.render_rays_infer
-        _fieldmlp.render_rays_infer = functools.partial(plain, prof=prof)
+        entry = "render_rays_infer_shaded" if shaded else "render_rays_infer"
+        plain = getattr(_fieldmlp, entry)
+        setattr(_fieldmlp, entry, functools.partial(plain, prof=prof))
         try:
             frame()
         finally:
-            _fieldmlp.render_rays_infer = plain
+            setattr(_fieldmlp, entry, plain)
         torch.cuda.synchronize()
         p = prof.cpu().tolist()
         tot = sum(p[:4])
