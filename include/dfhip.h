@@ -941,6 +941,37 @@ int dfhip_shading_backward_bf16(const float *sigma7, const void *albedo7, const 
 int dfhip_shading_light(const float *rays_o, uint64_t seed, uint64_t step, float *light,
                         dfhip_stream_t stream);
 
+/* ---- texture bake of export_mesh (csrc/texture.hip) -------------------------
+ * Replaces nvdiffrast's dr.rasterize + dr.interpolate in UV space
+ * (nerf/renderer.py:195-197) and the seam fill (renderer.py:243-256).  A
+ * texture is H rows of W texels; texel (r, c) has index r W + c and its centre
+ * at u = (c + 0.5) / W, v = (r + 0.5) / H.  All three are deterministic.
+ *
+ * dfhip_raster_uv_faces: vt [T, 2] f32 UVs, ft [F, 3] int32 rows of vt per
+ *   face -> face_id [H W] int32, the lowest face whose triangle covers the
+ *   texel centre, -1 where none does (the call fills face_id first).  A centre
+ *   is covered when the three edge functions (f32, texel units, relative to the
+ *   face's first vertex) all have one sign or are zero; either orientation.
+ *   Zero-area faces, faces outside the image and faces with an index >= T
+ *   cover nothing.  H W < 2^31, F < 2^31. */
+int dfhip_raster_uv_faces(const float *vt, const int32_t *ft, uint32_t F, uint32_t T, uint32_t H,
+                          uint32_t W, int32_t *face_id, dfhip_stream_t stream);
+/* v [V, 3] f32 positions, f [F, 3] int32 rows of v per face, face_id of
+ * dfhip_raster_uv_faces -> xyz [H W, 3] = w0 v[f0] + w1 v[f1] + w2 v[f2] and
+ * bary [H W, 2] = (w1, w2) (nullable), the barycentric weights of the texel
+ * centre in its face; zeros at uncovered texels (face_id outside [0, F), an
+ * index >= T or V, or a zero-area face). */
+int dfhip_raster_uv_interp(const float *vt, const int32_t *ft, const float *v, const int32_t *f,
+                           const int32_t *face_id, uint32_t F, uint32_t T, uint32_t V, uint32_t H,
+                           uint32_t W, float *xyz, float *bary, dfhip_stream_t stream);
+/* One dilation step of an [H, W, 3] uint8 image under an [H, W] uint8 mask
+ * (non-zero = covered) into dst_rgb / dst_mask (other buffers than the
+ * sources): a covered texel copies itself; an uncovered one takes the colour of
+ * its first covered neighbour in the order N, W, E, S, NW, NE, SW, SE (N = row
+ * r - 1) and becomes covered (mask 1); otherwise it is copied unchanged. */
+int dfhip_texture_dilate(const uint8_t *src_rgb, const uint8_t *src_mask, uint32_t H, uint32_t W,
+                         uint8_t *dst_rgb, uint8_t *dst_mask, dfhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

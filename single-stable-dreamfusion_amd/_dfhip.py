@@ -170,6 +170,10 @@ _SIGS = {
     "dfhip_freq_encode_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "dfhip_sh_encode_forward": [_i32, _vp, _vp, _u32, _u32, _u32, _vp, _vp],
     "dfhip_sh_encode_backward": [_i32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp],
+    "dfhip_raster_uv_faces": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
+    "dfhip_raster_uv_interp": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp,
+                               _vp],
+    "dfhip_texture_dilate": [_vp, _vp, _u32, _u32, _vp, _vp, _vp],
 }
 
 _lib = None

@@ -17,6 +17,9 @@ def get_parser():
     p.add_argument("-O2", action="store_true", help="equals --fp16 --dir_text")
     p.add_argument("--test", action="store_true", help="test mode")
     p.add_argument("--save_mesh", action="store_true")
+    p.add_argument("--mesh_texture_size", type=int, default=0,
+                   help="--save_mesh: 0 = vertex colours, N = bake an N x N albedo.png, "
+                        "-1 = automatic size")
     p.add_argument("--eval_interval", type=int, default=10)
     p.add_argument("--workspace", type=str, default="workspace")
     p.add_argument("--guidance", type=str, default="stable-diffusion",
@@ -79,6 +82,11 @@ def parse_opt(argv=None):
     return opt
 
 
+def mesh_texture_size(opt):
+    """--mesh_texture_size as Trainer.save_mesh's texture_size (-1 -> None)."""
+    return None if opt.mesh_texture_size < 0 else opt.mesh_texture_size
+
+
 def main(argv=None):
     from nerf.network_grid import NeRFNetwork
     from nerf.provider import NeRFDataset
@@ -98,7 +106,7 @@ def main(argv=None):
         for data in loader:
             trainer.test_step(data)
         if opt.save_mesh:
-            trainer.save_mesh(resolution=256)  # main.py:121-122
+            trainer.save_mesh(resolution=256, texture_size=mesh_texture_size(opt))  # main.py:121-122
         return
     train_loader = NeRFDataset(opt, device=device, type="train", H=opt.h, W=opt.w,
                                size=100).dataloader()
@@ -119,7 +127,7 @@ def main(argv=None):
     max_epoch = int(np.ceil(opt.iters / len(train_loader)))
     trainer.train(train_loader, None, max_epoch)
     if opt.save_mesh:
-        trainer.save_mesh(resolution=256)  # main.py:161-162
+        trainer.save_mesh(resolution=256, texture_size=mesh_texture_size(opt))  # main.py:161-162
 
 
 if __name__ == "__main__":

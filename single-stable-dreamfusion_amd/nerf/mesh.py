@@ -15,8 +15,16 @@ three libraries exists on this platform, so:
   are oriented with the density decreasing along the normal (outward).
   The surface is the same level set marching cubes approximates; the
   triangulation differs (more, smaller triangles);
-* the albedo is queried at the vertices and written as OBJ vertex colours
-  (`v x y z r g b`) instead of a UV-mapped texture image.
+* with `texture_size=0` (the default) the albedo is queried at the vertices
+  and written as OBJ vertex colours (`v x y z r g b`);
+* with a texture size the albedo is baked into `albedo.png` as the reference
+  does, without xatlas / nvdiffrast / cv2 / sklearn: `grid_atlas` gives every
+  face its own right-angled triangle of a regular grid of cells (the
+  marching-tetrahedra faces are near-uniform in size, so no chart solver is
+  needed), the HIP rasteriser of csrc/texture.hip finds the face and position
+  of every texel centre, `model.density` gives the albedo there, and a
+  3x3 dilation pads the seams (the reference fills them from a kd-tree
+  nearest neighbour).  See DESIGN.md "Texture bake".
 
 Vertices are mapped to [-1, 1] exactly as the reference does
 (`v / (resolution - 1) * 2 - 1`, renderer.py:149)."""
@@ -147,11 +155,174 @@ def write_obj(path, vertices, faces, colors=None):
         fp.writelines(f"f {a + 1} {b + 1} {c + 1}\n" for a, b, c in faces)
 
 
-def export_mesh(model, path, resolution=None, S=128, name=""):
+# ---------------------------------------------------------------- texture bake
+
+BAKE_CHUNK = 640000  # renderer.py:214 batch of the albedo query
+
+
+def _atlas_cell(ncells, H, W):
+    """Largest integer cell side s with (W // s) * (H // s) >= ncells (0 when
+    even s = 1 does not fit); the product does not grow with s."""
+    lo, hi = 0, min(H, W)
+    while lo < hi:
+        s = (lo + hi + 1) // 2
+        if (W // s) * (H // s) >= ncells:
+            lo = s
+        else:
+            hi = s - 1
+    return lo
+
+
+def grid_atlas(num_faces, size=None, min_cell=6, max_size=8192):
+    """A regular UV atlas: every face gets its own right-angled triangle.
+
+    The H x W texture (`size`: None = automatic, an int for a square, or
+    (H, W)) is cut into square cells of s texels, laid out row-major; cell k
+    holds faces 2k and 2k + 1.  Texel (row r, col c) has its centre at
+    u = (c + 0.5) / W, v = (r + 0.5) / H.  With n = s - 3 and (x, y) = (col,
+    row) texel coordinates relative to the cell's corner:
+
+      face 2k     (0.25, 0.25), (0.25 + n, 0.25), (0.25, 0.25 + n)
+                  covers the texels i, j >= 0, i + j <= n - 1
+      face 2k + 1 (b, b), (b - n, b), (b, b - n) with b = s - 1.25
+                  covers the texels i, j <= n + 1, i + j >= n + 3
+
+    so both cover n (n + 1) / 2 texel centres, every centre is at least 1/4
+    texel from the lines through the legs and 0.35 texel from the
+    hypotenuses, the two triangles of a cell and those of neighbouring cells
+    are 2 texels apart (Chebyshev), and both have the same orientation.
+
+    The automatic size is the smallest power of two >= 2048 whose cells are at
+    least `min_cell` texels.  Returns (vt [3 F, 2] float32 in [0, 1],
+    ft [F, 3] int32 = [3 i, 3 i + 1, 3 i + 2], H, W)."""
+    F = int(num_faces)
+    if F < 0:
+        raise ValueError("grid_atlas: num_faces must be >= 0")
+    if min_cell < 5:
+        raise ValueError("grid_atlas: min_cell must be >= 5 (3 texel centres per face)")
+    ncells = max(1, (F + 1) // 2)
+    trade = ("lower the mesh resolution or raise the texture size "
+             f"({F} faces need cells of >= {min_cell} texels)")
+    if size is None:
+        H = W = 2048
+        while _atlas_cell(ncells, H, W) < min_cell:
+            H = W = 2 * H
+            if H > max_size:
+                raise ValueError(f"grid_atlas: no texture up to {max_size}^2 fits; {trade}")
+    else:
+        H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        if H <= 0 or W <= 0 or max(H, W) > max_size:
+            raise ValueError(f"grid_atlas: texture size {H} x {W} outside [1, {max_size}]; {trade}")
+        if _atlas_cell(ncells, H, W) < min_cell:
+            raise ValueError(f"grid_atlas: a {H} x {W} texture is too small; {trade}")
+    s = _atlas_cell(ncells, H, W)
+    n, b = s - 3, s - 1.25
+    cols = W // s
+    cell = np.arange(F, dtype=np.int64) // 2
+    origin = np.stack([(cell % cols) * s, (cell // cols) * s], 1).astype(np.float64)  # x, y
+    lower = np.array([[0.25, 0.25], [0.25 + n, 0.25], [0.25, 0.25 + n]])
+    upper = np.array([[b, b], [b - n, b], [b, b - n]])
+    local = np.where((np.arange(F) % 2 == 0)[:, None, None], lower[None], upper[None])
+    xy = origin[:, None, :] + local  # [F, 3, 2] texel coordinates
+    vt = (xy / np.array([W, H], np.float64)).reshape(-1, 2).astype(np.float32)
+    ft = np.arange(3 * F, dtype=np.int32).reshape(F, 3)
+    return vt, ft, H, W
+
+
+def rasterize_uv(vt, ft, v, f, H, W):
+    """dr.rasterize + dr.interpolate of renderer.py:195-197 in UV space on the
+    HIP rasteriser: vt [T, 2] UVs, ft [F, 3], v [V, 3] positions, f [F, 3]
+    (arrays or device tensors) -> device tensors face_id [H, W] int32 (-1
+    where no face covers the texel centre), xyz [H, W, 3] f32 and
+    mask [H, W] bool."""
+    import _texture
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def dev_tensor(a, dtype):
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        return t.to(device=dev, dtype=dtype).contiguous()
+
+    vt, v = dev_tensor(vt, torch.float32), dev_tensor(v, torch.float32)
+    ft, f = dev_tensor(ft, torch.int32), dev_tensor(f, torch.int32)
+    face_id = _texture.raster_uv_faces(vt, ft, H, W)
+    xyz = _texture.raster_uv_interp(vt, ft, v, f, face_id, H, W)
+    face_id = face_id.view(H, W)
+    return face_id, xyz.view(H, W, 3), face_id >= 0
+
+
+@torch.no_grad()
+def query_texels(model, xyz, mask):
+    """The albedo of `model.density` at the masked texels of xyz [H, W, 3],
+    quantised as the reference does (renderer.py:235 truncation, after a clamp
+    to [0, 1]) -> [H, W, 3] uint8 image, zero where not masked."""
+    H, W = mask.shape
+    img = torch.zeros(H, W, 3, dtype=torch.uint8, device=xyz.device)
+    pts = xyz[mask]
+    if len(pts):
+        cols = []
+        for head in range(0, len(pts), BAKE_CHUNK):
+            feats = model.density(pts[head:head + BAKE_CHUNK].contiguous())["albedo"].float()
+            cols.append((feats.clamp(0, 1) * 255).to(torch.uint8))
+        img[mask] = torch.cat(cols)
+    return img
+
+
+@torch.no_grad()
+def bake_texture(model, xyz, mask, dilate=3):
+    """renderer.py:199-256: albedo at the covered texels, then `dilate` 3x3
+    dilation steps to pad the seams.  Returns (image [H, W, 3] uint8 on the
+    device, the mask before dilation)."""
+    import _texture
+    img = query_texels(model, xyz, mask)
+    img, _ = _texture.texture_dilate(img, mask.to(torch.uint8), dilate)
+    return img, mask
+
+
+def write_mtl(path, texture_name):
+    """The material of the textured OBJ (renderer.py:289-297)."""
+    with open(path, "w") as fp:
+        fp.write("# single-stable-dreamfusion_amd export_mesh material\n")
+        fp.write("newmtl mat0\n")
+        fp.write("Ka 1.000000 1.000000 1.000000\n")
+        fp.write("Kd 1.000000 1.000000 1.000000\n")
+        fp.write("Ks 0.000000 0.000000 0.000000\n")
+        fp.write("Tr 1.000000\n")
+        fp.write("illum 1\n")
+        fp.write("Ns 0.000000\n")
+        fp.write(f"map_Kd {texture_name}\n")
+
+
+def write_obj_textured(path, vertices, faces, vt, ft, mtl_name):
+    """Wavefront OBJ with texture coordinates (renderer.py:273-287): image row
+    0 is the top of the PNG, OBJ v = 0 the bottom, hence `vt u 1-v`."""
+    with open(path, "w") as fp:
+        fp.write("# single-stable-dreamfusion_amd export_mesh (marching tetrahedra, "
+                 "grid atlas)\n")
+        fp.write(f"mtllib {mtl_name}\n")
+        fp.writelines(f"v {a} {b} {c}\n" for a, b, c in vertices)
+        fp.writelines(f"vt {u} {1 - w}\n" for u, w in vt)
+        fp.write("usemtl mat0\n")
+        fp.writelines(f"f {a + 1}/{ta + 1} {b + 1}/{tb + 1} {c + 1}/{tc + 1}\n"
+                      for (a, b, c), (ta, tb, tc) in zip(faces, ft))
+
+
+def write_png(path, image):
+    """[H, W, 3] uint8 RGB, image row r = texel row r."""
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(image, np.uint8), "RGB").save(path)
+
+
+def export_mesh(model, path, resolution=None, S=128, name="", texture_size=0):
     """NeRFRenderer.export_mesh (renderer.py:121-299) without mcubes / xatlas /
     nvdiffrast: lattice query, marching tetrahedra at
-    min(mean_density, density_thresh), albedo at the vertices, `{name}mesh.obj`
-    under `path`.  Returns (vertices [V, 3] float32 in [-1, 1], faces [F, 3])."""
+    min(mean_density, density_thresh), then
+
+    * texture_size = 0: albedo at the vertices, `{name}mesh.obj` with vertex
+      colours under `path`;
+    * texture_size = None (automatic) or a positive size: `{name}mesh.obj`
+      with UVs, `{name}mesh.mtl` and the baked `{name}albedo.png`.
+
+    Returns (vertices [V, 3] float32 in [-1, 1], faces [F, 3])."""
     if resolution is None:
         resolution = model.grid_size
     mean = model.mean_density
@@ -161,13 +332,29 @@ def export_mesh(model, path, resolution=None, S=128, name=""):
     sig = query_lattice(model.density, resolution, S, device)
     verts, faces = isosurface(sig, thresh)
     verts = (verts / (resolution - 1.0) * 2 - 1).astype(np.float32)
-    colors = None
-    if len(verts):
-        cols = []
-        for head in range(0, len(verts), 640000):  # renderer.py:222 batch
-            chunk = torch.from_numpy(verts[head:head + 640000]).to(device).contiguous()
-            cols.append(model.density(chunk)["albedo"].float().cpu().numpy())
-        colors = np.clip(np.concatenate(cols), 0, 1)
+    faces = faces.astype(np.int32)
     os.makedirs(path, exist_ok=True)
-    write_obj(os.path.join(path, f"{name}mesh.obj"), verts, faces.astype(np.int32), colors)
-    return verts, faces.astype(np.int32)
+    obj = os.path.join(path, f"{name}mesh.obj")
+    if texture_size is not None and texture_size == 0:
+        colors = None
+        if len(verts):
+            cols = []
+            for head in range(0, len(verts), BAKE_CHUNK):
+                chunk = torch.from_numpy(verts[head:head + BAKE_CHUNK]).to(device).contiguous()
+                cols.append(model.density(chunk)["albedo"].float().cpu().numpy())
+            colors = np.clip(np.concatenate(cols), 0, 1)
+        write_obj(obj, verts, faces, colors)
+        return verts, faces
+    if len(faces) == 0:
+        # nothing to bake (and nothing launched): an empty OBJ and a black texel
+        vt, ft = np.zeros((0, 2), np.float32), np.zeros((0, 3), np.int32)
+        image = np.zeros((1, 1, 3), np.uint8)
+    else:
+        vt, ft, H, W = grid_atlas(len(faces), texture_size)
+        with torch.cuda.device(device):
+            _, xyz, mask = rasterize_uv(vt, ft, verts, faces, H, W)
+            image = bake_texture(model, xyz, mask)[0].cpu().numpy()
+    write_png(os.path.join(path, f"{name}albedo.png"), image)
+    write_mtl(os.path.join(path, f"{name}mesh.mtl"), f"{name}albedo.png")
+    write_obj_textured(obj, verts, faces, vt, ft, f"{name}mesh.mtl")
+    return verts, faces

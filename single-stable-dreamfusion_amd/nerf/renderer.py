@@ -151,13 +151,15 @@ class NeRFRenderer(nn.Module):
         self.local_step = 0
 
     @torch.no_grad()
-    def export_mesh(self, path, resolution=None, S=128):
+    def export_mesh(self, path, resolution=None, S=128, texture_size=0):
         """renderer.py:121-299: density on a resolution^3 lattice, isosurface at
         min(mean_density, density_thresh), `mesh.obj` under `path`.  mcubes /
-        xatlas / nvdiffrast do not exist here: marching tetrahedra and vertex
-        colours instead (nerf/mesh.py)."""
+        xatlas / nvdiffrast do not exist here: marching tetrahedra, and vertex
+        colours (texture_size = 0) or `mesh.mtl` + `albedo.png` baked on a
+        regular atlas (texture_size = None for automatic, or a size;
+        nerf/mesh.py)."""
         from .mesh import export_mesh
-        return export_mesh(self, path, resolution=resolution, S=S)
+        return export_mesh(self, path, resolution=resolution, S=S, texture_size=texture_size)
 
     def _bg(self, rays_d, bg_color):
         if self.bg_radius > 0:

@@ -747,14 +747,15 @@ class Trainer(object):
                 "depth": preds_depth[0].float().cpu().numpy()}
 
     # ------------------------------------------------------------ checkpoints
-    def save_mesh(self, save_path=None, resolution=128):
+    def save_mesh(self, save_path=None, resolution=128, texture_size=0):
         """utils.py:459-470: export the density isosurface under
-        `workspace/mesh` (NeRFRenderer.export_mesh, nerf/mesh.py)."""
+        `workspace/mesh` (NeRFRenderer.export_mesh, nerf/mesh.py);
+        texture_size as there (0 = vertex colours, None = automatic)."""
         if save_path is None:
             save_path = os.path.join(self.workspace, "mesh")
         self.log(f"==> Saving mesh to {save_path}")
         os.makedirs(save_path, exist_ok=True)
-        self.model.export_mesh(save_path, resolution=resolution)
+        self.model.export_mesh(save_path, resolution=resolution, texture_size=texture_size)
         self.log("==> Finished saving mesh.")
 
     def save_checkpoint(self, name=None, full=False, best=False):
