@@ -245,10 +245,16 @@ __device__ __forceinline__ bool load_pos(const float *__restrict__ inputs, const
 }
 
 // Slices touched by the corners of a cell at one level, as a bit mask of
-// W words (W = 1 for levels of at most 64 slices, else 2).
+// W words (W = 1 for levels of at most 64 slices, else 2).  ns: the level's
+// slices.  A dense level that is no power of two wraps nothing (MODE 0, wmask
+// all ones), yet with align_corners and an integer scale a sample at x = 1
+// has +1 corners of coordinate smul, past the tiled span:
+// their weight is exactly 0 and the walk skips their rows (past the level's
+// end), so a slice number past the level's slices — it would name a bin of
+// the next level — is dropped here.
 template <uint32_t D, int MODE, uint32_t W>
 __device__ __forceinline__ void slice_mask(const ge::LevelRows &lr, const uint32_t cell[D],
-                                           uint32_t shift, uint64_t (&mask)[W]) {
+                                           uint32_t shift, uint32_t ns, uint64_t (&mask)[W]) {
 #pragma unroll
     for (uint32_t h = 0; h < W; ++h) mask[h] = 0;
     if constexpr (MODE == 0 && D == 3) {
@@ -260,6 +266,7 @@ __device__ __forceinline__ void slice_mask(const ge::LevelRows &lr, const uint32
             if (k >> lr.lead) continue;
             const uint32_t o = (k & 1u) + ((k & 2u) ? lr.m1 : 0u) + ((k & 4u) ? lr.m2 : 0u);
             const uint32_t v = ((i0 + o) & lr.wmask) >> shift;
+            if (v >= ns) continue;  // a zero-weight corner past the level (see above)
             if constexpr (W == 1) {
                 mask[0] |= 1ull << v;
             } else {
@@ -273,6 +280,7 @@ __device__ __forceinline__ void slice_mask(const ge::LevelRows &lr, const uint32
     for (uint32_t k = 0; k < (1u << D); ++k) {
         if (k >> lr.lead) continue;
         const uint32_t v = ge::corner_row_m<D, MODE>(lr, cell, k) >> shift;
+        if (MODE == 0 && v >= ns) continue;
         if constexpr (W == 1) {
             mask[0] |= 1ull << v;
         } else {
@@ -327,19 +335,19 @@ __global__ __launch_bounds__(1024) void k_bin(const float *__restrict__ inputs,
                 float frac[D];
                 locate<D>(c, align, x, cell, frac);
                 const int mode = ge::row_mode(lr);
-                const uint32_t b0 = bi.bin0[l];
+                const uint32_t b0 = bi.bin0[l], ns = bi.bin0[l + 1] - b0;
                 const uint16_t id = (uint16_t)(s - tile * T);
-                if (bi.bin0[l + 1] - b0 <= 64) {  // uniform: one mask word
+                if (ns <= 64) {  // uniform: one mask word
                     uint64_t mask[1];
-                    if (mode == 0) slice_mask<D, 0, 1>(lr, cell, bi.shift, mask);
-                    else if (mode == 1) slice_mask<D, 1, 1>(lr, cell, bi.shift, mask);
-                    else slice_mask<D, 2, 1>(lr, cell, bi.shift, mask);
+                    if (mode == 0) slice_mask<D, 0, 1>(lr, cell, bi.shift, ns, mask);
+                    else if (mode == 1) slice_mask<D, 1, 1>(lr, cell, bi.shift, ns, mask);
+                    else slice_mask<D, 2, 1>(lr, cell, bi.shift, ns, mask);
                     append<1>(mask, b0, cnt, seg, id, T);
                 } else {
                     uint64_t mask[2];
-                    if (mode == 0) slice_mask<D, 0, 2>(lr, cell, bi.shift, mask);
-                    else if (mode == 1) slice_mask<D, 1, 2>(lr, cell, bi.shift, mask);
-                    else slice_mask<D, 2, 2>(lr, cell, bi.shift, mask);
+                    if (mode == 0) slice_mask<D, 0, 2>(lr, cell, bi.shift, ns, mask);
+                    else if (mode == 1) slice_mask<D, 1, 2>(lr, cell, bi.shift, ns, mask);
+                    else slice_mask<D, 2, 2>(lr, cell, bi.shift, ns, mask);
                     append<2>(mask, b0, cnt, seg, id, T);
                 }
             }
@@ -661,7 +669,15 @@ static bool make_fast_levels(const int32_t *offsets_host, const Levels &lv, cons
         const bool hashed = gridtype == 0 && stride > hsize;
         const bool pow2 = (hsize & (hsize - 1)) == 0;
         if (hashed || (!pow2 && span > hsize)) return false;  // not the mask form
-        if (bi.bin0[l + 1] - bi.bin0[l] > 64 || used == 0) return false;
+        const uint32_t ns = bi.bin0[l + 1] - bi.bin0[l];
+        if (ns > 64 || used == 0) return false;
+        // align_corners with an integer scale: at x = 1 the +1 corner (weight
+        // 0) has coordinate smul, so the unwrapped index of a dense level
+        // reaches smul (span - 1) / (smul - 1); k_bin_fast takes slice numbers
+        // from it unchecked, the generic k_bin drops those past the level
+        if (!pow2 && align && lv.scale[l] == floorf(lv.scale[l]) && smul > 1u &&
+            (uint64_t)smul * (span - 1u) / (smul - 1u) >= ((uint64_t)ns << bi.shift))
+            return false;
         fl.scale[l] = lv.scale[l];
         fl.lead[l] = used;
         fl.m1[l] = used > 1 ? smul : 0u;

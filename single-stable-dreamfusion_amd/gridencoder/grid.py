@@ -92,6 +92,16 @@ def binned_embedding_grad(grad_lbc, inputs, bound, offsets, offsets_host, B, m_d
     return out
 
 
+def _map_unit(x, bound):
+    """(x + bound) / (2 bound) as the kernels evaluate it for raw positions: a
+    correctly rounded f32 division.  Dividing by a Python scalar would not do:
+    torch multiplies by the scalar's reciprocal instead, which is an ulp off
+    for a quarter of the positions unless 2 bound is a power of two, and at the
+    fine levels an ulp of x is percents of a cell (the atomic backward then
+    weighed its corners at other positions than the forward did)."""
+    return (x + bound) / torch.full((), 2 * bound, dtype=x.dtype, device=x.device)
+
+
 class _grid_encode(Function):
     @staticmethod
     @custom_fwd(device_type="cuda")
@@ -170,7 +180,7 @@ class _grid_encode(Function):
             if dy_dx is not None:
                 dy_dx = dy_dx[:m]
             B = m
-        x01 = inputs if bound <= 0 else (inputs + bound) / (2 * bound)
+        x01 = inputs if bound <= 0 else _map_unit(inputs, bound)
         grad_embeddings = torch.zeros(rows, C, device=grad.device, dtype=table_dtype)
         grad_inputs = None
         if dy_dx is not None:

@@ -387,6 +387,135 @@ def test_grid_backward_is_adjoint_of_forward(rng):
     np.testing.assert_allclose((g * out).sum(), (gt * emb).sum(), rtol=1e-9)
 
 
+def test_grid_backward_is_adjoint_of_forward_align_corners(rng):
+    """The same with align_corners=True (offsets, strides and positions of the
+    aligned form), tiled and hashed."""
+    from gridencoder.grid import level_offsets
+    pls = np.exp2(np.log2(2048 / 16) / 15)
+    offs = level_offsets(16, 2, 3, 16, pls, 16, True)
+    S = float(np.float32(np.log2(pls)))
+    emb = rng.normal(size=(int(offs[-1]), 2)).astype(np.float64)
+    x = rng.random((100, 3), dtype=np.float32)
+    x[:3] = [[0, 0, 0], [1, 1, 1], [1, 0, 0.5]]
+    for gt in (1, 0):
+        out, _ = oracle.grid_encode_forward(x, emb, offs, S, 16, gridtype=gt, align_corners=True)
+        g = rng.normal(size=out.shape)
+        gt_emb = oracle.grid_encode_backward(g.astype(np.float64), x, offs, 2, S, 16, gridtype=gt,
+                                             align_corners=True)
+        np.testing.assert_allclose((g * out).sum(), (gt_emb * emb).sum(), rtol=1e-9)
+        assert np.abs(out).sum() > 0
+
+
+# An independent NumPy restatement of the encoder from its behavioural spec
+# (not from oracle.c): scale = 2^(l S) H - 1, res = ceil(scale) + 1, pos =
+# x scale + (align ? 0 : 0.5); corner index by strides of (align ? res : res + 1)
+# while stride <= rows; the spatial hash when gridtype == 0 and the stride
+# overflowed; always % rows; samples with a coordinate outside [0, 1] contribute
+# nothing.  With S = 1, H a power of two and x on the lattice k / 1024, scale is
+# an integer and pos is exact in f32 (fma or not), so the cell fractions are
+# multiples of 2^-10; a corner weight is the f32 rounding of their exact product
+# whatever the order of the f32 multiplies (any two fractions multiply exactly).
+# Embeddings and gradients are dyadic (multiples of 2^-6), so every product and
+# sum below is exact in float64 and the comparison is exact, not a tolerance.
+_PRIMES = (1, 2654435761, 805459861)
+
+
+def _np_grid_corners(x, offs, lvl, H, gridtype, align):
+    """Rows (absolute) [B, 2^D] and weights [B, 2^D] of every in-range sample
+    at one level, and the in-range mask."""
+    x64 = x.astype(np.float64)
+    ok = np.all((x64 >= 0) & (x64 <= 1), axis=1)
+    D = x.shape[1]
+    scale = 2.0 ** lvl * H - 1.0
+    res = int(np.ceil(scale)) + 1
+    side = res if align else res + 1
+    rows = int(offs[lvl + 1] - offs[lvl])
+    pos = x64[ok] * scale + (0.0 if align else 0.5)
+    cell = np.floor(pos)
+    frac = pos - cell
+    cell = cell.astype(np.uint64)
+    idx_all, w_all = [], []
+    for k in range(1 << D):
+        w = np.ones(len(pos))
+        idx = np.zeros(len(pos), np.uint64)
+        stride = 1
+        q = []
+        for d in range(D):
+            bit = (k >> d) & 1
+            w = w * (frac[:, d] if bit else 1.0 - frac[:, d])
+            q.append(cell[:, d] + np.uint64(bit))
+        for d in range(D):
+            if stride > rows:
+                break
+            idx = idx + q[d] * np.uint64(stride)
+            stride *= side
+        if gridtype == 0 and stride > rows:
+            idx = np.zeros(len(pos), np.uint64)
+            for d in range(D):
+                idx ^= (q[d] * np.uint64(_PRIMES[d])) & np.uint64(0xFFFFFFFF)
+        idx_all.append(int(offs[lvl]) + (idx % np.uint64(rows)).astype(np.int64))
+        w_all.append(w.astype(np.float32).astype(np.float64))  # the kernel's weights are f32
+    return np.stack(idx_all, 1), np.stack(w_all, 1), ok
+
+
+def _np_grid_forward(x, emb, offs, H, gridtype, align):
+    L, C = len(offs) - 1, emb.shape[1]
+    out = np.zeros((x.shape[0], L * C))
+    for lvl in range(L):
+        idx, w, ok = _np_grid_corners(x, offs, lvl, H, gridtype, align)
+        out[ok, lvl * C:(lvl + 1) * C] = (w[:, :, None] * emb[idx]).sum(1)
+    return out
+
+
+def _np_grid_backward(g, x, offs, C, H, gridtype, align):
+    L = len(offs) - 1
+    gemb = np.zeros((int(offs[-1]), C))
+    for lvl in range(L):
+        idx, w, ok = _np_grid_corners(x, offs, lvl, H, gridtype, align)
+        gl = g[ok, lvl * C:(lvl + 1) * C]
+        np.add.at(gemb, idx.reshape(-1), (w[:, :, None] * gl[:, None, :]).reshape(-1, C))
+    return gemb
+
+
+def _np_grid_layout(name, D, align):
+    """(offsets, H): a level_offsets layout whose upper levels are capped (L = 5,
+    H = 4, scale 2, 2^10 or 2^7 rows), or a hand-built one whose levels are all
+    smaller than their tiled span and no power of two (modulo wrap; L = 3,
+    H = 16: spans 17^D / 33^D / 65^D, or 16^D / 32^D / 64^D aligned)."""
+    from gridencoder.grid import level_offsets
+    if name == "offsets":
+        return level_offsets(5, 2, D, 4, 2.0, 10 if D == 3 else 7, align), 4
+    rows = [4000, 30000, 100000] if D == 3 else [250, 1000, 3000]
+    return np.concatenate([[0], np.cumsum(rows)]).astype(np.int32), 16
+
+
+@pytest.mark.parametrize("layout", ["offsets", "modulo"])
+@pytest.mark.parametrize("D", [3, 2])
+@pytest.mark.parametrize("gridtype", [1, 0])
+@pytest.mark.parametrize("align", [False, True])
+def test_grid_oracle_equals_numpy_spec(align, gridtype, D, layout):
+    offs, H = _np_grid_layout(layout, D, align)
+    L, C = len(offs) - 1, 2
+    rng = np.random.default_rng(100 + 8 * D + 2 * gridtype + align)
+    x = (rng.integers(0, 1025, (1500, D)) / 1024).astype(np.float32)
+    x[:6] = np.array([[0, 0, 0], [1, 1, 1], [1, 0, 0.5], [1025 / 1024, 0.5, 0.5],
+                      [0.5, -1 / 1024, 0.5], [0.25, 1, 0.75]], np.float32)[:, :D]
+    emb = rng.integers(-128, 129, (int(offs[-1]), C)) / 64.0
+    g = rng.integers(-128, 129, (x.shape[0], L * C)) / 64.0
+    want = _np_grid_forward(x, emb, offs, H, gridtype, align)
+    got, _ = oracle.grid_encode_forward(x, emb, offs, 1.0, H, gridtype=gridtype,
+                                        align_corners=align)
+    assert got.dtype == np.float64
+    assert np.all(want[3:5] == 0) and np.count_nonzero(want) > 0.9 * want.size
+    np.testing.assert_allclose(got, want, rtol=1e-12, atol=0)
+    wantb = _np_grid_backward(g, x, offs, C, H, gridtype, align)
+    gotb = oracle.grid_encode_backward(g, x, offs, C, 1.0, H, gridtype=gridtype,
+                                       align_corners=align)
+    for lvl in range(L):  # every level's row block is exercised
+        assert np.count_nonzero(wantb[offs[lvl]:offs[lvl + 1]]) > 0, lvl
+    np.testing.assert_allclose(gotb, wantb, rtol=0, atol=1e-12 * np.abs(wantb).max())
+
+
 def test_grid_dy_dx_matches_finite_difference(rng):
     offs, S = _grid_setup()
     emb = rng.normal(size=(int(offs[-1]), 2)).astype(np.float64)
