@@ -427,6 +427,39 @@ int dfhip_mlp_backward(int elem, const void *x, const float *w1, const float *b1
                        float *gb2, float *gw3, float *gb3, int accumulate,
                        dfhip_stream_t stream);
 
+/* ---------------------------------------------------------------- fused vanilla field
+ * Replaces the torch ops of nerf/network.py:104-115 (common_forward of the
+ * vanilla backbone) under fp16 autocast: the degree-6 frequency encoding
+ * (freqencoder.cu:28-58, f32), the residual MLP of network.py:13-67 (four
+ * ResBlocks 39 -> 128 -> 128 -> 128 -> 128: Linear -> LayerNorm -> + skip ->
+ * SiLU, then Linear(128, 4)), sigma = trunc_exp(h0 + 5 exp(-|x|^2/0.08))
+ * (f32), albedo = sigmoid(h[1:4]) (f16).  Linears are f16 GEMMs with f32
+ * accumulation and f16 outputs, LayerNorm / residual / SiLU run in f32.
+ * params: host array of 19 device pointers to the f32 tensors in
+ * sigma_net.state_dict() order: net.0.dense.weight [128,39], net.0.dense.bias,
+ * net.0.norm.weight, net.0.norm.bias, net.0.skip.weight [128,39]; for l = 1..3
+ * net.l.dense.weight [128,128], net.l.dense.bias, net.l.norm.weight,
+ * net.l.norm.bias; net.4.weight [4,128], net.4.bias [4].
+ * xyz: [M, 3] f32 positions. */
+uint32_t dfhip_resmlp_params(void); /* 61188 */
+int dfhip_resmlp_field_forward(const float *xyz, const float *const *params, float *sigma,
+                               void *albedo, uint32_t M, dfhip_stream_t stream);
+/* Backward (network.py:104-115 through autograd; :135-146, :165-173 for dx):
+ * recomputes the forward, nothing is saved between the two calls.  grad_sigma
+ * [M] f32, grad_albedo [M, 3] (grad_albedo_dtype F16 / F32).  grads: host array
+ * of 19 device pointers shaped as params (f32; overwritten, or added into with
+ * accumulate), or NULL for none.  dx: [M, 3] f32 input gradient (encoder chain
+ * rule freqencoder.cu:63-94 plus the Gaussian term), or NULL.  With grads NULL
+ * only dx is computed: the normal query is this call with grad_sigma = 1 and
+ * grad_albedo = 0.  scratch: dfhip_resmlp_field_backward_scratch(M) bytes,
+ * 16-byte aligned.  Deterministic (no float atomics: per-split partials
+ * summed in a fixed order). */
+uint64_t dfhip_resmlp_field_backward_scratch(uint32_t M);
+int dfhip_resmlp_field_backward(const float *xyz, const float *const *params,
+                                const float *grad_sigma, const void *grad_albedo,
+                                int grad_albedo_dtype, uint32_t M, float *dx, void *scratch,
+                                float *const *grads, int accumulate, dfhip_stream_t stream);
+
 /* Fused grid field (native path of nerf/field.py): tiled-grid encoding
  * (gridencoder.cu:75-178 arithmetic, f16 table) + the MLP/heads above in ONE
  * kernel.  xyz: [cap, 3] f32 in [-bound, bound] (mapped to [0,1] as

@@ -1,0 +1,87 @@
+"""Native fused vanilla field (csrc/resmlp.hip): frequency encoding (degree
+6) -> residual MLP 39 -> 128 x4 -> 4 -> trunc_exp density with the Gaussian
+blob and sigmoid albedo (reference nerf/network.py:13-115 under fp16
+autocast), forward and backward, on MFMA.  No reference pybind counterpart:
+the reference runs this as torch ops."""
+import ctypes
+
+import torch
+
+import _dfhip as _d
+from _dfhip import call, checked, ptr, stream
+
+IN, HIDDEN, OUT, BLOCKS = 39, 128, 4, 4
+# rows of one MFMA tile (a wave's samples per pass) and rows a workgroup of
+# the forward kernel takes per pass (8 waves)
+ROW_TILE, WORKGROUP_ROWS = 16, 128
+
+# sigma_net.state_dict() order (include/dfhip.h)
+SHAPES = ([(HIDDEN, IN), (HIDDEN,), (HIDDEN,), (HIDDEN,), (HIDDEN, IN)]
+          + [(HIDDEN, HIDDEN), (HIDDEN,), (HIDDEN,), (HIDDEN,)] * (BLOCKS - 1)
+          + [(OUT, HIDDEN), (OUT,)])
+
+
+def params_count():
+    return int(_d.load().dfhip_resmlp_params())
+
+
+def backward_scratch_bytes(M):
+    return int(_d.load().dfhip_resmlp_field_backward_scratch(int(M)))
+
+
+def _f32(t, what):
+    checked(t, what)
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{what} must be a float32 tensor")
+
+
+def _pointers(ts, what):
+    if len(ts) != len(SHAPES):
+        raise RuntimeError(f"expected the {len(SHAPES)} sigma_net tensors in state_dict order")
+    for i, (t, shp) in enumerate(zip(ts, SHAPES)):
+        _f32(t, f"{what}{i}")
+        if tuple(t.shape) != shp:
+            raise RuntimeError(f"{what}{i} must have shape {shp}, got {tuple(t.shape)}")
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def field_forward(xyz, params, sigma, albedo):
+    """xyz [M, 3] f32 -> sigma [M] f32, albedo [M, 3] f16."""
+    M = xyz.shape[0]
+    _f32(xyz, "xyz")
+    _f32(sigma, "sigma")
+    checked(albedo, "albedo")
+    if tuple(xyz.shape) != (M, 3) or tuple(sigma.shape) != (M,) or \
+            tuple(albedo.shape) != (M, 3) or albedo.dtype != torch.float16:
+        raise RuntimeError("xyz [M, 3] f32, sigma [M] f32 and albedo [M, 3] f16 expected")
+    call("dfhip_resmlp_field_forward", ptr(xyz), _pointers(params, "param"), ptr(sigma),
+         ptr(albedo), M, stream())
+
+
+def field_backward(xyz, params, grad_sigma, grad_albedo, dx=None, grads=None, accumulate=False,
+                   scratch=None):
+    """grads: the 19 f32 gradients shaped as params (overwritten, or added
+    into with accumulate) or None; dx: [M, 3] f32 input gradient or None.
+    scratch: uint8 tensor of backward_scratch_bytes(M) or None (allocated)."""
+    M = xyz.shape[0]
+    _f32(xyz, "xyz")
+    _f32(grad_sigma, "grad_sigma")
+    checked(grad_albedo, "grad_albedo")
+    if grad_albedo.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("grad_albedo must be float16 or float32")
+    if tuple(xyz.shape) != (M, 3) or tuple(grad_sigma.shape) != (M,) or \
+            tuple(grad_albedo.shape) != (M, 3):
+        raise RuntimeError("xyz [M, 3], grad_sigma [M] and grad_albedo [M, 3] expected")
+    if dx is not None:
+        _f32(dx, "dx")
+        if tuple(dx.shape) != (M, 3):
+            raise RuntimeError("dx must be [M, 3]")
+    need = backward_scratch_bytes(M)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=xyz.device)
+    checked(scratch, "scratch", "u8")
+    if scratch.numel() < need:
+        raise RuntimeError(f"scratch must hold {need} bytes")
+    call("dfhip_resmlp_field_backward", ptr(xyz), _pointers(params, "param"), ptr(grad_sigma),
+         ptr(grad_albedo), _d.dtype_code(grad_albedo, "grad_albedo"), M, ptr(dx), ptr(scratch),
+         None if grads is None else _pointers(grads, "grad"), int(bool(accumulate)), stream())

@@ -1,5 +1,5 @@
 """Command line of the SDS trainer (mirror of reference main.py:12-162, grid
-backbone).  Flag names and defaults are the reference's, because the whole
+and vanilla backbones).  Flag names and defaults are the reference's, because the whole
 `opt` namespace is forwarded as renderer kwargs (utils.py:363)."""
 import argparse
 import os
@@ -79,7 +79,23 @@ def parse_opt(argv=None):
         opt.fp16, opt.dir_text = True, True
     if opt.bf16:
         opt.fp16 = False  # -O --bf16: the C5 option replaces fp16 autocast
+    if opt.backbone == "vanilla":
+        # the vanilla field's regularisers (reference main.py:86-89)
+        opt.lambda_entropy = 0
+        opt.lambda_opacity = 1e-3
     return opt
+
+
+def network_class(opt):
+    """The NeRFNetwork class of --backbone: `grid` (nerf/network_grid.py) or
+    `vanilla` (nerf/network.py)."""
+    if opt.backbone == "grid":
+        from nerf.network_grid import NeRFNetwork
+    elif opt.backbone == "vanilla":
+        from nerf.network import NeRFNetwork
+    else:
+        raise NotImplementedError(f"--backbone {opt.backbone} is not implemented")
+    return NeRFNetwork
 
 
 def mesh_texture_size(opt):
@@ -88,14 +104,12 @@ def mesh_texture_size(opt):
 
 
 def main(argv=None):
-    from nerf.network_grid import NeRFNetwork
     from nerf.provider import NeRFDataset
     from nerf.sd import InjectedSDS, StableDiffusion, SyntheticSDS
     from nerf.utils import Trainer, make_adam, seed_everything
 
     opt = parse_opt(argv)
-    if opt.backbone != "grid":
-        raise NotImplementedError(f"--backbone {opt.backbone} is not implemented")
+    NeRFNetwork = network_class(opt)
     seed_everything(opt.seed)
     model = NeRFNetwork(opt)
     device = torch.device("cuda")
