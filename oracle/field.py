@@ -428,11 +428,14 @@ def ray_tail(ws, depth, image, nears, fars, bg):
 
 def entropy(ws, lam):
     """utils.py:386-391: lam * mean(-a log2 a - (1-a) log2(1-a)), a = clamp(ws,
-    1e-5, 1-1e-5); returns (loss f64, d loss / d ws f64)."""
+    1e-5, 1-1e-5); returns (loss f64, d loss / d ws f64).  ws is a float32
+    tensor there, so the two thresholds are the float32 values F32(1e-5) and
+    F32(1) - F32(1e-5): torch.clamp's backward passes the gradient AT them."""
     w = np.asarray(ws, F64)
-    a = np.clip(w, 1e-5, 1 - 1e-5)
+    lo, hi = F64(F32(1e-5)), F64(F32(1) - F32(1e-5))
+    a = np.clip(w, lo, hi)
     e = -a * np.log2(a) - (1 - a) * np.log2(1 - a)
-    inside = (w >= 1e-5) & (w <= 1 - 1e-5)
+    inside = (w >= lo) & (w <= hi)
     g = np.where(inside, lam / w.size * (np.log2(1 - a) - np.log2(a)), 0.0)
     return lam * e.mean(), g
 

@@ -54,9 +54,9 @@ __device__ __forceinline__ void load_w(W &w, const float *w1, const float *b1, c
 // The network kernels give each ray kSub = 16 lanes (consecutive threads):
 // sub-lane q makes frequency column q (q < 12) and hidden units
 // [kPer q, kPer q + kPer), the output layer's partial sums are combined with
-// four xor-shuffles (the same order in all sixteen lanes).  A block is 16
-// rays; 16k rays are 4096 waves (4 per SIMD; four lanes per ray left one wave
-// per SIMD to hide every LDS and global latency).
+// four xor-shuffles (the same order in all sixteen lanes).  A wave is four
+// rays; 16k rays are 4096 waves (4 per SIMD; an earlier four-lanes-per-ray
+// layout left one wave per SIMD to hide every LDS and global latency).
 // Workgroups of 64 rays (1,024 threads): every workgroup stages the f16
 // weights once and the backward writes one weight-gradient partial per
 // workgroup, so 64 rays per workgroup instead of 16 load the weights and write
@@ -86,8 +86,8 @@ __device__ __forceinline__ void features_part(const float *d, int q, float *sx) 
     }
 }
 
-// This sub-lane's 16 hidden units (f16 values) and the full f16 output
-// pre-activation (partials combined across the ray's four lanes).
+// This sub-lane's kPer = 4 hidden units (f16 values) and the full f16 output
+// pre-activation (partials combined across the ray's sixteen lanes).
 __device__ __forceinline__ void mlp_part(const W &w, const float *x, int q, float h[kPer],
                                         float o[kOut]) {
     static_assert(kPer == 4, "one float4 of hidden units per sub-lane");
@@ -243,7 +243,7 @@ struct FwdIO {
     uint8_t *mask;
 };
 
-// Network backward: the forward is recomputed (four lanes per ray), then the
+// Network backward: the forward is recomputed (kSub = 16 lanes per ray), then the
 // sigmoid and the two f16 Linear layers are run backward and this block's
 // weight-gradient partials (f32 sums over its 64 rays of f16 products) formed
 // from LDS images of the activations.  FWD: the recomputed forward is also the

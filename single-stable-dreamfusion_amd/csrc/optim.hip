@@ -8,11 +8,22 @@
 //   1. k_nonfinite: found_inf = any(!isfinite(grad)) over every tensor
 //      (torch._amp_foreach_non_finite_check_and_unscale_ with inv_scale 1,
 //      as GradScaler._check_inf_per_device does for a fused optimizer);
-//   2. k_adam: if !found_inf, per element exactly torch's fused Adam
+//   2. k_adam: if !found_inf, per element the formula of torch's fused Adam
 //      (the bias corrections, per-tensor constants, are evaluated once per
-//      block with the same f32 expressions; blocks map to tensors through a
-//      block table and stream float4s)
-//      (ATen FusedAdamKernel / fused_adam_utils.cuh, ADAM mode, no amsgrad):
+//      block; blocks map to tensors through a block table and stream float4s)
+//      (ATen FusedAdamKernel / fused_adam_utils.cuh, ADAM mode, no amsgrad).
+//      Everything here is f32, one rounding per operation.  torch's kernel
+//      is NOT: it holds lr, the betas, eps and weight_decay as double, so
+//      `beta1 * exp_avg + (1 - beta1) * grad` (and the v line, the weight
+//      decay and the two bias corrections 1 - pow(beta, step)) are evaluated
+//      in double and rounded to f32 once, while this C ABI receives the
+//      hyper-parameters as float.  The two therefore differ by the rounding
+//      of the hyper-parameters themselves — 1 - float(0.99) is 9.5e-7
+//      relative off 0.01, 1 - float(0.9) 2.4e-7 off 0.1 — on top of a few
+//      f32 roundings per element: about 1e-6 relative on exp_avg_sq and on
+//      the update, which tests/test_gpu_optim.py allows against torch and
+//      bounds by rounding count against the float64 oracle (oracle/optim.py)
+//      evaluated at the float32-rounded hyper-parameters.
 //        g = grad / scale;  g += wd * p
 //        m = b1 * m + (1 - b1) * g;  v = b2 * v + (1 - b2) * g * g
 //        step_size = lr / (1 - b1^t);  denom = sqrt(v) / sqrt(1 - b2^t) + eps
@@ -113,7 +124,7 @@ __device__ __forceinline__ void adam_chunk(const Batch &B, uint32_t blk, float s
     const int ti = chunk_tensor(B, blk);
     const Tensor &t = B.t[ti];
     const uint64_t e0 = (uint64_t)(blk - t.block0) * kPerBlock;
-    // per-tensor constants (the same f32 expressions torch evaluates per element)
+    // per-tensor constants (torch evaluates them per element, and in double)
     const float step = *t.step + 1.0f;
     AdamK k;
     k.s = scale;
@@ -215,7 +226,10 @@ static int adam_amp_step(int count, float *const *params, const float *const *gr
     B.lr_dev = lr_dev;
     uint32_t blocks = 0;
     for (int k = 0; k < count; ++k) {
-        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || !steps[k]) {
+        // an empty tensor has no storage (torch gives it a null pointer); only
+        // its step count is touched
+        const bool data = params[k] && grads[k] && exp_avg[k] && exp_avg_sq[k];
+        if (!steps[k] || (numel[k] != 0 && !data)) {
             set_error("%s: null pointer in tensor %d", name, k);
             return DFHIP_EINVAL;
         }

@@ -43,7 +43,8 @@ def eligible(optimizer, scaler, unit_scale=False):
         if torch.is_tensor(g["lr"]):
             return False
         for p in g["params"]:
-            if not (p.is_cuda and p.dtype == torch.float32):
+            # the kernel walks parameter, gradient and moments as flat memory
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 return False
             n += 1
     return 0 < n <= _MAX_TENSORS
@@ -68,6 +69,18 @@ class NativeAdamAmp:
             st["step"] = st["step"].to(device=p.device, dtype=torch.float32)
         return st
 
+    def _key(self):
+        """What the cached descriptor arrays were built from: the optimizer's
+        state dict (a reloaded state is a new dict), every gradient buffer
+        (-1: no gradient; an empty tensor's pointer is 0) and every group's
+        betas / eps / weight_decay, so a change of any of them after the first
+        step rebuilds the arrays as torch's optimizer re-reads them."""
+        opt = self.optimizer
+        return (id(opt.state), len(opt.state),
+                *(p.grad.data_ptr() if p.grad is not None else -1
+                  for g in opt.param_groups for p in g["params"]),
+                *((g["betas"], g["eps"], g["weight_decay"]) for g in opt.param_groups))
+
     def step(self):
         """One scaler.step(optimizer) + scaler.update() (parameters without a
         gradient are skipped, as torch does)."""
@@ -86,12 +99,10 @@ class NativeAdamAmp:
             growth, backoff, interval = 1.0, 1.0, 1 << 30
         if self.found_inf is None:
             self.found_inf = torch.zeros(1, dtype=torch.float32, device=scale.device)
-        # fast path: same parameters / gradient buffers as last step (the graph-
-        # replayed step keeps its gradients in place) -> only the lrs are new
-        # (a reloaded optimizer state is a new dict: its identity is part of the key)
-        key = (id(self.optimizer.state), len(self.optimizer.state),
-               *(p.grad.data_ptr() if p.grad is not None else 0
-                 for g in self.optimizer.param_groups for p in g["params"]))
+        # fast path: same parameters / gradient buffers / group hyper-parameters
+        # as last step (the graph-replayed step keeps its gradients in place)
+        # -> only the lrs are new
+        key = self._key()
         if key != self._ptr_key:
             self._rebuild(key)
         if self._arrays is None:
@@ -115,7 +126,10 @@ class NativeAdamAmp:
         reads lr_dev[its group]): captured once in the native train step's
         HIP graph (nerf/graph.py), while the prologue launch writes lr_dev
         every step from group_lrs().  Built against the current gradient
-        buffers and optimizer state, like step()'s fast path."""
+        buffers and optimizer state, like step()'s fast path.  By design the
+        closure (and the graph that captured it) holds the groups' betas, eps
+        and weight_decay by value: unlike step(), which re-reads them, a later
+        change of those needs a new device_lr_launch and a new capture."""
         sc = self.scaler
         if sc.is_enabled():
             if sc._scale is None:
@@ -131,9 +145,7 @@ class NativeAdamAmp:
             growth, backoff, interval = 1.0, 1.0, 1 << 30
         if self.found_inf is None:
             self.found_inf = torch.zeros(1, dtype=torch.float32, device=scale.device)
-        key = (id(self.optimizer.state), len(self.optimizer.state),
-               *(p.grad.data_ptr() if p.grad is not None else 0
-                 for g in self.optimizer.param_groups for p in g["params"]))
+        key = self._key()
         self._rebuild(key)
         if self._arrays is None:
             raise RuntimeError("device_lr_launch: no parameter has a gradient")
@@ -163,6 +175,13 @@ class NativeAdamAmp:
             for p in g["params"]:
                 if p.grad is None:
                     continue
+                gr = p.grad
+                if not (gr.is_cuda and gr.dtype == torch.float32 and gr.is_contiguous()
+                        and gr.shape == p.shape):
+                    raise RuntimeError(
+                        "NativeAdamAmp: a gradient must be a contiguous float32 GPU tensor of "
+                        f"its parameter's shape {tuple(p.shape)} (got {gr.dtype}, shape "
+                        f"{tuple(gr.shape)}, strides {gr.stride()}, {gr.device})")
                 st = self._state(p)
                 ts.append((p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["step"], gi, b1, b2,
                            g["eps"], g["weight_decay"]))

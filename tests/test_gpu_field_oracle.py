@@ -226,47 +226,9 @@ def test_field_chain_matches_oracle(gpu, seed, emb_scale):
 def test_ray_head_matches_oracle(gpu):
     """Background MLP + mix + depth + mask (csrc/head.hip) against
     oracle.field.bg_forward / ray_tail; background weight gradients against the
-    exact f16-graph sums; grad_ws = -sum_c g_c bg_c."""
-    from nerf import head as _head
+    exact f16-graph sums; grad_ws = -sum_c g_c bg_c.  (The comparison itself:
+    oracle_checks.check_ray_head, shared with test_gpu_head_edges.py.)"""
+    from oracle_checks import check_ray_head, ray_head_inputs
     torch.manual_seed(3)
-    N = 16384
     l1, l2 = nn.Linear(39, 64).to(gpu), nn.Linear(64, 3).to(gpu)
-    g = torch.Generator(device="cpu").manual_seed(4)
-    d = torch.randn(N, 3, generator=g)
-    d = (d / d.norm(dim=1, keepdim=True)).to(gpu)
-    ws = torch.rand(N, generator=g).to(gpu)
-    depth = (torch.rand(N, generator=g) * 2).to(gpu)
-    image = torch.rand(N, 3, generator=g).to(gpu)
-    nears = (torch.rand(N, generator=g) * 0.5 + 0.2).to(gpu)
-    fars = nears + (torch.rand(N, generator=g) * 2 - 0.1).to(gpu)
-    ws.requires_grad_(True)
-    image.requires_grad_(True)
-    out_img, out_depth, mask = _head.ray_head(ws, depth, image, d, nears, fars, None, (l1, l2))
-    wts = [t.detach().cpu().numpy() for t in (l1.weight, l1.bias, l2.weight, l2.bias)]
-    bo = of.bg_forward(d.cpu().numpy(), wts)
-    ei, ed, em = of.ray_tail(ws.detach().cpu().numpy(), depth.cpu().numpy(),
-                             image.detach().cpu().numpy(), nears.cpu().numpy(),
-                             fars.cpu().numpy(), bo["bg"].astype(np.float32))
-    gi = out_img.detach().t().cpu().numpy()
-    # colour: (1 - ws) times the background's f16 window, plus the f32 mix
-    bb = of.bg_bounds(bo, wts, acc_ulps=None)  # VALU fmaf chains: order-free bound
-    one_m = (1.0 - ws.detach().cpu().numpy().astype(np.float64))[:, None]
-    win = one_m * bb["dbg"] + 2 * 2.0 ** -24 * np.abs(ei)
-    diff = np.abs(gi.astype(np.float64) - ei)
-    assert np.all(diff <= win), f"colour outside its window: {(diff - win).max():.3e}"
-    print(f"\nbackground colour differs on {(diff > 0).any(1).mean():.2e} of rays")
-    np.testing.assert_array_equal(out_depth.detach().cpu().numpy(), ed)
-    np.testing.assert_array_equal(mask.cpu().numpy(), em)
-    gimg = torch.randn(3, N, generator=g).to(gpu) * 1e-2
-    grads = torch.autograd.grad(out_img, [ws, image, l1.weight, l1.bias, l2.weight, l2.bias],
-                                gimg)
-    gimg_np = gimg.t().cpu().numpy().astype(np.float32)
-    np.testing.assert_array_equal(grads[1].cpu().numpy(), gimg_np)
-    want_ws = -(gimg_np.astype(np.float64) * bo["bg"].astype(np.float64)).sum(1)
-    np.testing.assert_allclose(grads[0].cpu().numpy(), want_ws, rtol=2e-3, atol=1e-7)
-    gbg = gimg_np * (np.float32(1) - ws.detach().cpu().numpy())[:, None]
-    bw = of.bg_bounds(bo, wts, gbg)
-    for i, (a, b, w) in enumerate(zip(grads[2:], of.bg_backward(bo, wts, gbg), bw["grads"])):
-        a = a.cpu().numpy().astype(np.float64).reshape(b.shape)
-        err = np.abs(a - b)
-        assert np.all(err <= w), f"bg param {i}: worst excess {(err - w).max():.3e}"
+    check_ray_head(gpu, 16384, l1, l2, ray_head_inputs(16384, 4))

@@ -217,6 +217,35 @@ def test_native_adam_unit_scale_only_for_bf16():
     assert not eligible(opt, None, unit_scale=True)
 
 
+def test_native_adam_eligibility_without_a_device():
+    """What eligible() refuses without a device: a subclass of Adam, another
+    optimizer, a CPU parameter; and the key of the
+    cached descriptors holds every group's betas / eps / weight_decay."""
+    import torch
+    from nerf.optim import NativeAdamAmp, eligible
+
+    class MyAdam(torch.optim.Adam):
+        pass
+
+    p = torch.nn.Parameter(torch.zeros(4))
+    on = torch.amp.GradScaler("cuda", enabled=False)  # accepted with unit_scale=True
+    assert not eligible(MyAdam([p], lr=1e-3), on, unit_scale=True)
+    assert not eligible(torch.optim.SGD([p], lr=1e-3), on, unit_scale=True)
+    assert not eligible(torch.optim.Adam([p], lr=1e-3), on, unit_scale=True)  # CPU parameter
+    opt = torch.optim.Adam([p], lr=1e-3)
+    nat = NativeAdamAmp(opt, on)
+    k0 = nat._key()
+    opt.param_groups[0]["lr"] = 0.5  # re-read every step: not part of the key
+    assert nat._key() == k0
+    for name, val in (("weight_decay", 0.1), ("betas", (0.5, 0.9)), ("eps", 1e-3)):
+        opt.param_groups[0][name] = val
+        k1 = nat._key()
+        assert k1 != k0, name
+        k0 = k1
+    p.grad = torch.zeros(4)
+    assert nat._key() != k0
+
+
 def test_module_breakdown_counts_whole_steps(tmp_path):
     """bench._module_breakdown: per-step kernel time over whole steps between
     march count launches; the last step and anything after it are ignored."""

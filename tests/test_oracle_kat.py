@@ -605,3 +605,153 @@ def test_sh_jacobian_finite_difference(rng):
         xm[:, d] -= eps
         fd = (oracle.sh_encode(xp, 8)[0] - oracle.sh_encode(xm, 8)[0]) / (2 * eps)
         np.testing.assert_allclose(jac[:, d], fd, rtol=1e-5, atol=1e-5)
+
+
+# ---------------------------------------------------------------- Adam + GradScaler oracle
+
+def _torch_adam_run(wd, steps=4):
+    """oracle.optim against torch.optim.Adam (non-fused, CPU float64) over a few
+    steps, two tensors, the second without a gradient on step 1."""
+    import oracle.optim as oo
+    rng = np.random.default_rng(5)
+    shapes = [(7, 3), (5,)]
+    hyper = (3e-2, 0.8, 0.95, 1e-8, wd)
+    ps = [torch.tensor(rng.standard_normal(s), dtype=torch.float64, requires_grad=True)
+          for s in shapes]
+    opt = torch.optim.Adam(ps, lr=hyper[0], betas=hyper[1:3], eps=hyper[3], weight_decay=wd,
+                           foreach=False, fused=False)
+    P = [p.detach().numpy().copy() for p in ps]
+    M = [np.zeros(s) for s in shapes]
+    V = [np.zeros(s) for s in shapes]
+    S, scale, tracker = [0.0, 0.0], 1.0, 0
+    for it in range(steps):
+        gs = [rng.standard_normal(s) * 10.0 ** rng.integers(-3, 2) for s in shapes]
+        if it == 1:
+            gs[1] = None
+        for p, g in zip(ps, gs):
+            p.grad = None if g is None else torch.tensor(g)
+        opt.step()
+        P, M, V, S, scale, tracker, inf = oo.amp_adam_step(P, gs, M, V, S, [hyper] * 2, scale,
+                                                           tracker, 1 << 30)
+        assert not inf and scale == 1.0 and tracker == it + 1
+        for k, p in enumerate(ps):
+            st = opt.state[p]
+            assert float(st["step"]) == S[k]
+            np.testing.assert_allclose(P[k], p.detach().numpy(), rtol=1e-12, atol=1e-15)
+            np.testing.assert_allclose(M[k], st["exp_avg"].numpy(), rtol=1e-12, atol=1e-18)
+            np.testing.assert_allclose(V[k], st["exp_avg_sq"].numpy(), rtol=1e-12, atol=1e-24)
+    assert S == [float(steps), float(steps - 1)]  # the tensor without a gradient lags by one
+
+
+@pytest.mark.parametrize("wd", [0.0, 0.01])
+def test_adam_oracle_matches_torch_f64(wd):
+    _torch_adam_run(wd)
+
+
+def test_adam_oracle_unscales_and_skips():
+    """grad / scale enters the update; a non-finite gradient anywhere skips
+    every tensor (parameters, moments, steps unchanged)."""
+    import oracle.optim as oo
+    p, g = [np.array([1.0, -2.0]), np.array([0.5])], [np.array([8.0, -4.0]), np.array([2.0])]
+    z = [np.zeros(2), np.zeros(1)]
+    h = [(0.1, 0.9, 0.99, 0.0, 0.0)] * 2
+    # t = 1, eps = 0: m / (sqrt(v) / sqrt(1 - b2)) / (1 - b1) = sign(g) -> p -= lr sign(g)
+    P, M, V, S, scale, tr, inf = oo.amp_adam_step(p, g, z, z, [0, 0], h, 4.0, 0, 2000)
+    np.testing.assert_allclose(P[0], [0.9, -1.9], rtol=1e-15)
+    np.testing.assert_allclose(P[1], [0.4], rtol=1e-15)
+    np.testing.assert_allclose(M[0], [0.2, -0.1], rtol=1e-15)     # (1 - 0.9) * g / 4
+    np.testing.assert_allclose(V[0], [0.04, 0.01], rtol=1e-13)    # (1 - 0.99) * (g / 4)^2
+    assert (S, scale, tr, inf) == ([1.0, 1.0], 4.0, 1, False)
+    for bad in (np.inf, -np.inf, np.nan):
+        gb = [g[0], np.array([bad])]
+        P2, M2, V2, S2, scale2, tr2, inf2 = oo.amp_adam_step(P, gb, M, V, S, h, scale, tr, 2000)
+        assert inf2 and (S2, scale2, tr2) == ([1.0, 1.0], 2.0, 0)
+        for a, b in zip(P2 + M2 + V2, P + M + V):
+            assert np.array_equal(a, b)
+
+
+def test_scale_update_sequences():
+    """torch._amp_update_scale_ by hand: growth after `interval` clean steps,
+    backoff and tracker reset on inf, no growth to a non-finite float32."""
+    import oracle.optim as oo
+    seq = [False, False, True, False, True, False, False, False]
+    want = [(8.0, 1), (16.0, 0), (8.0, 0), (8.0, 1), (4.0, 0), (4.0, 1), (8.0, 0), (8.0, 1)]
+    scale, tr, got = 8.0, 0, []
+    for inf in seq:
+        scale, tr = oo.update_scale(scale, tr, inf, 2)
+        got.append((scale, tr))
+    assert got == want
+    big = 2.0 ** 127
+    assert oo.update_scale(big, 0, False, 1) == (big, 0)      # 2^128 is not a float32
+    assert oo.update_scale(big, 0, True, 1) == (2.0 ** 126, 0)
+    assert oo.update_scale(2.0 ** 126, 0, False, 1) == (big, 0)
+    # against torch's own kernel on the CPU
+    for s0, t0, inf, interval in [(8.0, 0, 0.0, 2), (8.0, 1, 0.0, 2), (8.0, 1, 1.0, 2),
+                                  (big, 0, 0.0, 1)]:
+        s, t = torch.tensor([s0]), torch.tensor([t0], dtype=torch.int32)
+        torch._amp_update_scale_(s, t, torch.tensor([inf]), 2.0, 0.5, interval)
+        assert oo.update_scale(s0, t0, bool(inf), interval) == (float(s), int(t))
+
+
+def test_adam_bounds_hold_for_float32_evaluation():
+    """The rounding-count bounds of test_gpu_optim (tests/optim_cases.py) on
+    the case's own inputs: a np.float32 evaluation of the formula, one
+    rounding per operation, lies inside them at every step, and no constant is
+    more than four times what that evaluation needs (the pow terms evaluated
+    at numpy's own measured pow error, so only the counted constants remain)."""
+    import optim_cases as oc
+    P = oc.params()
+    M = [np.zeros_like(p) for p in P]
+    V = [np.zeros_like(p) for p in P]
+    scale = oc.INIT_SCALE
+    worst = {"m": 0.0, "v": 0.0, "d": 0.0, "ds": 0.0}
+    need = [dict(worst) for _ in oc.GROUPS]
+    for it in range(oc.STEPS):
+        G = oc.grads(it, scale)
+        for k, gi in enumerate(oc.GROUP):
+            h = oc.hyper32(gi)
+            new = oc.adam_f32(P[k], G[k], M[k], V[k], it, scale, *h)
+            bd = oc.bounds(P[k], G[k], M[k], V[k], it, scale, *h)
+            for q, r in oc.ratios(bd, P[k], *new).items():
+                worst[q] = max(worst[q], r)
+            own = oc.bounds(P[k], G[k], M[k], V[k], it, scale, *h,
+                            pow_ulps1=oc.pow_ulps(h[1], it + 1), pow_ulps2=oc.pow_ulps(h[2], it + 1))
+            for q, r in oc.ratios(own, P[k], *new).items():
+                need[gi][q] = max(need[gi][q], r)
+            P[k], M[k], V[k] = new
+    print("\nfloat32 evaluation, worst error / bound:", worst, "own pow error:", need)
+    assert max(worst.values()) <= 1.0, worst
+    for gi, n in enumerate(need):
+        assert min(n.values()) >= 0.25, (gi, n)
+
+
+# ---------------------------------------------------------------- entropy oracle
+
+def test_entropy_oracle_thresholds_are_float32():
+    """oracle.field.entropy against torch CPU autograd of utils.py:386-391 on
+    the two clamp thresholds and their float32 neighbours: torch.clamp's
+    backward passes the gradient AT a threshold, and the thresholds are float32
+    values (ws is a float32 tensor)."""
+    import oracle.field as of
+    f32 = np.float32
+    lo, hi = f32(1e-5), f32(1) - f32(1e-5)
+    assert hi == f32(1 - 1e-5)  # the kernel's 1.0f - 1e-5f is torch's float32(1 - 1e-5)
+    up, dn = f32(np.inf), f32(-np.inf)
+    ws = np.array([0, 1, 0.5, lo, hi, np.nextafter(lo, dn), np.nextafter(hi, dn),
+                   np.nextafter(lo, up), np.nextafter(hi, up)], f32)
+    lam = 0.7
+    w = torch.tensor(ws, requires_grad=True)
+    w.clamp(1e-5, 1 - 1e-5).sum().backward()
+    mask = w.grad.numpy() != 0
+    assert mask.tolist() == [False, False, True, True, True, False, True, True, False]
+    a = w.detach().clamp(1e-5, 1 - 1e-5).double().requires_grad_()
+    loss = lam * (-a * torch.log2(a) - (1 - a) * torch.log2(1 - a)).mean()
+    loss.backward()
+    want_g = np.where(mask, a.grad.numpy(), 0.0)
+    got_loss, got_g = of.entropy(ws, lam)
+    np.testing.assert_allclose(got_loss, float(loss.detach()), rtol=1e-12)
+    np.testing.assert_allclose(got_g, want_g, rtol=1e-12, atol=0)
+    nz = np.arange(9) != 2  # 0.5: inside, and its gradient log2(.5) - log2(.5) is 0
+    assert np.array_equal(got_g[nz] != 0, mask[nz]) and got_g[2] == 0
+    # the magnitude at the thresholds: log2((1 - 1e-5) / 1e-5) lam / N
+    np.testing.assert_allclose(np.abs(got_g[[3, 4]]), 16.6096 * lam / 9, rtol=2e-4)
