@@ -178,6 +178,18 @@ int dfhip_march_rays_train_count_staged(int dtype, const void *rays_o, const voi
                                         int32_t *counter, const void *noises,
                                         int32_t *block_sums, float *stage,
                                         dfhip_stream_t stream);
+/* dfhip_march_rays_train_count_staged and dfhip_grid_quads (elem, embeddings
+ * ... quads: its arguments, Hb its H) in ONE launch: the workgroups after the
+ * march's own build the table copy and the corner quads, 1,024 threads each,
+ * while the longest rays finish.  Neither role reads what the other writes;
+ * every output is bit-identical to the two launches'.  rows > 0, N > 0. */
+int dfhip_march_rays_train_count_staged_quads(
+    int dtype, const void *rays_o, const void *rays_d, const uint8_t *grid, float bound,
+    float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, const void *nears,
+    const void *fars, int32_t *rays, int32_t *counter, const void *noises, int32_t *block_sums,
+    float *stage, int elem, const float *embeddings, const int32_t *offsets, uint32_t L,
+    float S, uint32_t Hb, uint32_t gridtype, int align_corners, uint32_t rows, void *table,
+    void *quads, dfhip_stream_t stream);
 int dfhip_march_rays_train_emit_staged(int dtype, const void *rays_d, uint32_t max_steps,
                                        uint32_t N, uint32_t M, void *xyzs, void *dirs,
                                        void *deltas, int32_t *rays, const int32_t *block_sums,
@@ -545,6 +557,36 @@ int dfhip_grid_field_backward_bf16(const void *enc, const float *xyz, float boun
                                    void *d_enc_lbc, float *mlp_partial, uint32_t mlp_parts,
                                    float *gw1, float *gb1, float *gw2, float *gb2, float *gw3,
                                    float *gb3, int accumulate, dfhip_stream_t stream);
+/* The field backward without an embedding gradient (dfhip_grid_field_backward
+ * with grad_embeddings NULL for elem DFHIP_F16, dfhip_grid_field_backward_bf16
+ * for DFHIP_BF16) with the overflow check of the six weight gradients where
+ * they are written: a weight-sum workgroup that writes a non-finite value
+ * (with accumulate: the sum written) stores 1.0f to found_inf[0] (NULL: no
+ * check; never cleared here, see dfhip_adam_amp_step_tail). */
+int dfhip_grid_field_backward_check(int elem, const void *enc, const float *xyz, float bound,
+                                    const float *w1, const float *b1, const float *w2,
+                                    const float *b2, const float *w3, const float *b3,
+                                    const float *grad_sigma, const void *grad_rgb,
+                                    int grad_rgb_dtype, uint32_t cap, const int32_t *m_dev,
+                                    void *d_enc_lbc, float *mlp_partial, uint32_t mlp_parts,
+                                    float *gw1, float *gb1, float *gw2, float *gb2, float *gw3,
+                                    float *gb3, int accumulate, float *found_inf,
+                                    int defer_sum, dfhip_stream_t stream);
+/* The parameter-gradient sums of a train step in ONE launch, issued after the
+ * field backward: the field backward's weight-gradient sum (of a
+ * dfhip_grid_field_backward_check call with defer_sum = 1, which then launches
+ * none and leaves mlp_partial for this call), the ray head's (head_partial !=
+ * NULL: of a dfhip_ray_head_forward_backward_entropy_loss_check call with
+ * defer_sum = 1, N its ray count) and the entropy loss (ws != NULL: loss[0] =
+ * dfhip_entropy_forward's value).  The role of a workgroup is chosen by its
+ * index; each role keeps the summation order of its own launch, so every
+ * output is bit-identical to the separate launches'.  found_inf as in the
+ * _check entries (covers the field's and the head's gradients). */
+int dfhip_param_grad_sums(const float *mlp_partial, uint32_t mlp_parts, float *gw1, float *gb1,
+                          float *gw2, float *gb2, float *gw3, float *gb3, int accumulate,
+                          uint32_t N, const float *head_partial, float *hgw1, float *hgb1,
+                          float *hgw2, float *hgb2, const float *ws, float lambda, float *loss,
+                          float *found_inf, dfhip_stream_t stream);
 
 /* Binned owner-computes form of grid_encode_backward (gridencoder.cu:226-313,
  * csrc/gridbin.hip) for D = 3, C in {1, 2, 4}: (sample, level) pairs are binned
@@ -624,6 +666,11 @@ typedef struct dfhip_binned_opts {
                                    workgroup {bin, XCC id << 32 | HW_ID, parts, entries,
                                    t0 (start), t1 (plan done), part, t2 (end)} (every walk
                                    form, wall clock at 100 MHz); NULL = off */
+    float *found_inf;           /* NULL = off.  The GradScaler overflow check where the
+                                   gradient is written: a sum workgroup that writes a
+                                   non-finite value into grad_embeddings (with accumulate:
+                                   the sum written) stores 1.0f here.  Never cleared by
+                                   this call; see dfhip_adam_amp_step_tail */
 } dfhip_binned_opts;
 /* dfhip_grid_backward_binned_scratch / dfhip_grid_encode_backward_binned_stencil
  * with per-call options (group 1 = single samples, eps ignored; group 7 =
@@ -677,6 +724,34 @@ int dfhip_adam_amp_step_lr_dev(int count, float *const *params, const float *con
                                float *scale, int32_t *growth_tracker, float *found_inf,
                                float growth_factor, float backoff_factor, int growth_interval,
                                dfhip_stream_t stream);
+/* dfhip_adam_amp_step_lr_dev as the tail of a replayed train step: the same
+ * arithmetic on the same state, bit for bit.
+ *
+ * Overflow check.  Bit k of covered_mask says that every writer of grads[k]
+ * since the last step reported a non-finite value it wrote into *found_inf
+ * (dfhip_binned_opts.found_inf, dfhip_grid_field_backward_check,
+ * dfhip_ray_head_*_check, dfhip_param_grad_sums); the re-reading check runs
+ * over the other tensors only and is not launched when there are none (or
+ * they are all empty).  A gradient changed after it was written (an
+ * all-reduce) is not covered.
+ * Who zeroes *found_inf: this call, once per step, in its finalize launch (as
+ * the other two entries do); nobody else.  The caller allocates it zeroed,
+ * and a caller that runs checking writers WITHOUT this call after them (a dry
+ * run) zeroes it itself before the next step, or a stale 1 skips that step.
+ *
+ * Live count.  With live != NULL the finalize launch also copies live[0..2)
+ * (the march's sample counter) to live_rows[2 * live_row[0] ..] (live_row: a
+ * device word, dfhip_train_step_prologue_row), instead of a device-to-device
+ * copy after the step. */
+int dfhip_adam_amp_step_tail(int count, float *const *params, const float *const *grads,
+                             float *const *exp_avg, float *const *exp_avg_sq,
+                             float *const *steps, const uint64_t *numel, const int32_t *lr_slot,
+                             const float *lr_dev, const float *beta1, const float *beta2,
+                             const float *eps, const float *weight_decay, float *scale,
+                             int32_t *growth_tracker, float *found_inf, float growth_factor,
+                             float backoff_factor, int growth_interval, uint32_t covered_mask,
+                             const int32_t *live, int32_t *live_rows, const int32_t *live_row,
+                             dfhip_stream_t stream);
 /* Per-ray tail of run_cuda (nerf/renderer.py:536-551, csrc/head.hip).
  * Forward: bg = sigmoid(W2 relu(W1 freq6(rays_d) + b1) + b2) with the
  * reference's fp16 autocast rounding (w1 != NULL: W1 [64, 39], b1 [64], W2
@@ -733,6 +808,28 @@ int dfhip_ray_head_forward_backward_entropy_loss(
     const float *b2, float *out_image, float *out_depth, uint8_t *mask, const float *g_image,
     float *grad_image, float *grad_ws, float *partial, float *gw1, float *gb1, float *gw2,
     float *gb2, const float *grad_loss, float lambda, float *loss, dfhip_stream_t stream);
+/* The two entries above with the overflow check of the background network's
+ * gradients where they are written: a weight-sum workgroup that writes a
+ * non-finite gw1 / gb1 / gw2 / gb2 value stores 1.0f to found_inf[0] (NULL:
+ * no check; never cleared here, see dfhip_adam_amp_step_tail).
+ * dfhip_ray_head_backward_check is dfhip_ray_head_backward (grad_loss NULL),
+ * _entropy (grad_loss, loss NULL) or _entropy_loss (both given).  defer_sum
+ * != 0: no weight-sum launch (and no loss) here; the caller runs
+ * dfhip_param_grad_sums on `partial` later. */
+int dfhip_ray_head_backward_check(uint32_t N, const float *g_image, const float *ws,
+                                  const float *rays_d, const float *w1, const float *b1,
+                                  const float *w2, const float *b2, const float *bg_color,
+                                  float *grad_image, float *grad_ws, float *grad_bg,
+                                  float *partial, float *gw1, float *gb1, float *gw2, float *gb2,
+                                  const float *grad_loss, float lambda, float *loss,
+                                  float *found_inf, dfhip_stream_t stream);
+int dfhip_ray_head_forward_backward_entropy_loss_check(
+    uint32_t N, const float *ws, const float *depth, const float *image, const float *rays_d,
+    const float *nears, const float *fars, const float *w1, const float *b1, const float *w2,
+    const float *b2, float *out_image, float *out_depth, uint8_t *mask, const float *g_image,
+    float *grad_image, float *grad_ws, float *partial, float *gw1, float *gb1, float *gw2,
+    float *gb2, const float *grad_loss, float lambda, float *loss, float *found_inf,
+    int defer_sum, dfhip_stream_t stream);
 
 /* nerf/utils.py:386-391 entropy regulariser: loss[0] = lambda * mean(-a log2 a
  * - (1 - a) log2(1 - a)), a = clamp(ws, 1e-5, 1 - 1e-5) (f64 sum); backward
@@ -778,6 +875,17 @@ int dfhip_train_step_prologue_lr(const float *pose, float fx, float fy, float cx
                                  float *bg_color, float *g_image, int32_t *counter,
                                  const float *lr_host, uint32_t n_lr, float *lr_dev,
                                  dfhip_stream_t stream);
+/* The same launch also writing row_dev[0] = row (row_dev DEVICE int32, NULL:
+ * not written): the row of the model's step_counter that the step's last
+ * launch (dfhip_adam_amp_step_tail) copies this step's sample count into. */
+int dfhip_train_step_prologue_row(const float *pose, float fx, float fy, float cx, float cy,
+                                  uint32_t H, uint32_t W, const float *aabb, float min_near,
+                                  uint64_t seed, uint64_t step, int perturb, const float *alphas,
+                                  uint32_t min_step, uint32_t max_step, float *rays_o,
+                                  float *rays_d, float *nears, float *fars, float *noises,
+                                  float *bg_color, float *g_image, int32_t *counter,
+                                  const float *lr_host, uint32_t n_lr, float *lr_dev,
+                                  uint32_t row, int32_t *row_dev, dfhip_stream_t stream);
 
 /* nerf/renderer.py:496-532 — the inference branch of run_cuda (the host loop
  * of march_rays raymarching.cu:700-804 -> network_grid.common_forward

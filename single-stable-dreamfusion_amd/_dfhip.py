@@ -131,6 +131,25 @@ _SIGS = {
                             _vp, _vp, _f32, _f32, _i32, _vp],
     "dfhip_adam_amp_step_lr_dev": [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp],
+    "dfhip_adam_amp_step_tail": [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _f32, _f32, _i32, _u32, _vp, _vp, _vp, _vp],
+    "dfhip_ray_head_backward_check": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp],
+    "dfhip_ray_head_forward_backward_entropy_loss_check": [_u32] + [_vp] * 22 + [_f32, _vp, _vp,
+                                                                                 _i32, _vp],
+    "dfhip_param_grad_sums": [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _u32, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _f32, _vp, _vp, _vp],
+    "dfhip_grid_field_backward_check": [_i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _i32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _i32, _vp, _i32, _vp],
+    "dfhip_march_rays_train_count_staged_quads": [_i32, _vp, _vp, _vp, _f32, _f32, _u32, _u32,
+                                                  _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _i32, _vp, _vp, _u32, _f32, _u32, _u32, _i32,
+                                                  _u32, _vp, _vp, _vp],
+    "dfhip_train_step_prologue_row": [_vp, _f32, _f32, _f32, _f32, _u32, _u32, _vp, _f32,
+                                      ctypes.c_uint64, ctypes.c_uint64, _i32, _vp, _u32, _u32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp,
+                                      _u32, _vp, _vp],
     "dfhip_ray_head_forward": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp, _vp, _vp],
     "dfhip_ray_head_backward": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

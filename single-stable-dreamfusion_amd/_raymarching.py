@@ -105,6 +105,38 @@ def march_rays_train_count_staged(rays_o, rays_d, grid, bound, dt_gamma, max_ste
          ptr(noises), ptr(block_sums), ptr(stage), stream())
 
 
+def march_rays_train_count_staged_quads(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H,
+                                        nears, fars, rays, counter, noises, block_sums, stage,
+                                        embeddings, offsets, S, Hb, gridtype, align_corners,
+                                        table, quads):
+    """march_rays_train_count_staged with _fieldmlp.grid_quads's work (the
+    table copy and corner quads of `embeddings`) done by extra workgroups of
+    the same launch.  f32 rays; same outputs as the two calls."""
+    dt = _f(rays_o, "rays_o")
+    checked(grid, "grid", "u8")
+    checked(block_sums, "block_sums", "int")
+    checked(stage, "stage")
+    if stage.dtype != torch.float32 or stage.numel() < march_rays_train_stage_floats(N, max_steps):
+        raise RuntimeError("stage must be float32 with march_rays_train_stage_floats(N, max_steps) "
+                           "elements")
+    checked(embeddings, "embeddings")
+    checked(table, "table")
+    checked(quads, "quads", "int")
+    checked(offsets, "offsets", "int")
+    rows = embeddings.shape[0]
+    if embeddings.dtype != torch.float32 or tuple(embeddings.shape) != (rows, 2) or \
+            table.dtype not in (torch.float16, torch.bfloat16) or tuple(table.shape) != (rows, 2):
+        raise RuntimeError("embeddings [rows, 2] f32 and table [rows, 2] f16 / bf16 expected")
+    if tuple(quads.shape) != (rows, 4):
+        raise RuntimeError("quads must be a [rows, 4] int32 tensor")
+    elem = _d.BF16 if table.dtype == torch.bfloat16 else _d.F16
+    call("dfhip_march_rays_train_count_staged_quads", dt, ptr(rays_o), ptr(rays_d), ptr(grid),
+         bound, dt_gamma, max_steps, N, C, H, ptr(nears), ptr(fars), ptr(rays), ptr(counter),
+         ptr(noises), ptr(block_sums), ptr(stage), elem, ptr(embeddings), ptr(offsets),
+         offsets.shape[0] - 1, float(S), int(Hb), int(gridtype), int(bool(align_corners)), rows,
+         ptr(table), ptr(quads), stream())
+
+
 def march_rays_train_emit_staged(rays_d, max_steps, N, M, xyzs, dirs, deltas, rays, block_sums,
                                  zero_tail, stage):
     """march_rays_train_emit from the count pass's stage (no second march)."""

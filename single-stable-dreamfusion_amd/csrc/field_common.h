@@ -447,5 +447,105 @@ __device__ __forceinline__ uint32_t active_count(const int32_t *m_dev, uint32_t 
     return m < 0 ? 0u : ((uint32_t)m < cap ? (uint32_t)m : cap);
 }
 
+// The autocast table (f32 embeddings rounded to the element type, as
+// grid.py:38-39's cast) and its corner quads for QUAD forwards, rows first,
+// first + stride, ... of `rows` by this thread (a whole workgroup calls it:
+// the level constants are staged in LDS first); quad entries of hashed /
+// modulo levels and corners past a dense level's end (never read: a
+// reachable cell's corners are rows of its level) are left zero.  A row's
+// words depend on the embeddings alone, not on which thread makes them:
+// k_grid_quads (fieldmlp.hip) and the rider workgroups of the march's count
+// launch (raymarching.hip) write the same bits.
+template <typename E>
+__device__ __forceinline__ void grid_quads_rows(const float *__restrict__ emb,
+                                                const int32_t *__restrict__ offsets,
+                                                const ge::Levels &lv, uint32_t gridtype,
+                                                int align_corners, uint32_t rows, uint32_t first,
+                                                uint32_t stride, uint32_t *__restrict__ table,
+                                                u32x4 *__restrict__ quads) {
+    __shared__ LevelK LK[kLevels];
+    __shared__ uint32_t OFF[kLevels + 1];
+    stage_levels(LK, offsets, lv, gridtype, align_corners != 0);
+    for (int l = threadIdx.x; l <= kLevels; l += blockDim.x) OFF[l] = (uint32_t)offsets[l];
+    __syncthreads();
+    const float2 *e2 = reinterpret_cast<const float2 *>(emb);
+    auto pack = [&](uint32_t row) {
+        const float2 f = e2[row];
+        E v[2] = {(E)f.x, (E)f.y};
+        uint32_t u;
+        __builtin_memcpy(&u, v, 4);
+        return u;
+    };
+    // u64 counter: first + k * stride may pass 2^32 before it passes rows
+    for (uint64_t r64 = first; r64 < rows; r64 += stride) {
+        const uint32_t row = (uint32_t)r64;
+        table[row] = pack(row);
+        int l = 0;
+        while (l < kLevels - 1 && row >= OFF[l + 1]) ++l;
+        const LevelK k = LK[l];
+        u32x4 q = {0u, 0u, 0u, 0u};
+        if (k.flags == 0u) {
+            const uint32_t r = row - k.base, n = OFF[l + 1] - OFF[l];
+            const uint32_t o[4] = {0u, 1u, k.m1, k.m1 + 1u};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t idx = (r + o[j]) & k.wmask;
+                if (idx < n) q[j] = pack(k.base + idx);
+            }
+        }
+        quads[row] = q;
+    }
+}
+
+// Sum the per-workgroup partials of the field backward (fixed order) into the
+// six f32 gradients: block blk of ceil(kParams / 64) takes 64 parameters; its
+// 16 part-lanes sum the parts p = j, j+16, ... of each, then lane j = 0 adds
+// the 16 lane sums in order.  1,024 threads.  found_inf (null: off): a
+// workgroup that writes a non-finite value stores 1.0f there (the GradScaler
+// overflow check where the gradient is written).  Every thread of the
+// workgroup returns from here (no early exit: the caller may be a kernel
+// with other roles).
+__device__ __forceinline__ void wgrad_sum_block(uint32_t blk, const float *__restrict__ partial,
+                                                uint32_t parts, float *gw1, float *gb1,
+                                                float *gw2, float *gb2, float *gw3, float *gb3,
+                                                int accumulate, float *found_inf) {
+    __shared__ float lane_sum[16][64];
+    const int col = threadIdx.x & 63, j = threadIdx.x >> 6;
+    const int i = blk * 64 + col;
+    float s = 0.0f;
+    if (i < kParams) {
+        // parts j, j + 16, ... added in that order; eight loads in flight
+        uint32_t p = j;
+        for (; p + 7 * 16 < parts; p += 8 * 16) {
+            float x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = partial[(size_t)(p + 16 * u) * kParams + i];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += x[u];
+        }
+        for (; p < parts; p += 16) s += partial[(size_t)p * kParams + i];
+    }
+    lane_sum[j][col] = s;
+    __syncthreads();
+    bool bad = false;
+    if (j == 0 && i < kParams) {
+        s = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) s += lane_sum[q][col];
+        float *dst;
+        int k;
+        if (i < kOffB1) { dst = gw1; k = i - kOffW1; }
+        else if (i < kOffW2) { dst = gb1; k = i - kOffB1; }
+        else if (i < kOffB2) { dst = gw2; k = i - kOffW2; }
+        else if (i < kOffW3) { dst = gb2; k = i - kOffB2; }
+        else if (i < kOffB3) { dst = gw3; k = i - kOffW3; }
+        else { dst = gb3; k = i - kOffB3; }
+        const float w = accumulate ? dst[k] + s : s;
+        bad = !isfinite(w);
+        dst[k] = w;
+    }
+    if (found_inf && __syncthreads_or(bad) && threadIdx.x == 0) *found_inf = 1.0f;
+}
+
 }  // namespace fm
 }  // namespace dfhip

@@ -572,38 +572,11 @@ __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
 __global__ __launch_bounds__(1024) void k_field_wgrad_sum(const float *__restrict__ partial,
                                                           uint32_t parts, float *gw1, float *gb1,
                                                           float *gw2, float *gb2, float *gw3,
-                                                          float *gb3, int accumulate) {
-    __shared__ float lane_sum[16][64];
-    const int col = threadIdx.x & 63, j = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + col;
-    float s = 0.0f;
-    if (i < kParams) {
-        // parts j, j + 16, ... added in that order; eight loads in flight
-        uint32_t p = j;
-        for (; p + 7 * 16 < parts; p += 8 * 16) {
-            float x[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) x[u] = partial[(size_t)(p + 16 * u) * kParams + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += x[u];
-        }
-        for (; p < parts; p += 16) s += partial[(size_t)p * kParams + i];
-    }
-    lane_sum[j][col] = s;
-    __syncthreads();
-    if (j != 0 || i >= kParams) return;
-    s = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += lane_sum[q][col];
-    float *dst;
-    int k;
-    if (i < kOffB1) { dst = gw1; k = i - kOffW1; }
-    else if (i < kOffW2) { dst = gb1; k = i - kOffB1; }
-    else if (i < kOffB2) { dst = gw2; k = i - kOffW2; }
-    else if (i < kOffW3) { dst = gb2; k = i - kOffB2; }
-    else if (i < kOffB3) { dst = gw3; k = i - kOffW3; }
-    else { dst = gb3; k = i - kOffB3; }
-    dst[k] = accumulate ? dst[k] + s : s;
+                                                          float *gb3, int accumulate,
+                                                          float *found_inf = nullptr) {
+    // (the body is field_common.h's: head.hip's merged sum launch runs it too)
+    wgrad_sum_block(blockIdx.x, partial, parts, gw1, gb1, gw2, gb2, gw3, gb3, accumulate,
+                    found_inf);
 }
 
 static uint32_t bwd_blocks(uint32_t M) {
@@ -950,37 +923,10 @@ __global__ __launch_bounds__(256) void k_grid_quads(const float *__restrict__ em
                                                     int align_corners, uint32_t rows,
                                                     uint32_t *__restrict__ table,
                                                     u32x4 *__restrict__ quads) {
-    __shared__ LevelK LK[kLevels];
-    __shared__ uint32_t OFF[kLevels + 1];
-    stage_levels(LK, offsets, lv, gridtype, align_corners != 0);
-    for (int l = threadIdx.x; l <= kLevels; l += blockDim.x) OFF[l] = (uint32_t)offsets[l];
-    __syncthreads();
-    const float2 *e2 = reinterpret_cast<const float2 *>(emb);
-    auto pack = [&](uint32_t row) {
-        const float2 f = e2[row];
-        E v[2] = {(E)f.x, (E)f.y};
-        uint32_t u;
-        __builtin_memcpy(&u, v, 4);
-        return u;
-    };
-    for (uint32_t row = blockIdx.x * blockDim.x + threadIdx.x; row < rows;
-         row += gridDim.x * blockDim.x) {
-        table[row] = pack(row);
-        int l = 0;
-        while (l < kLevels - 1 && row >= OFF[l + 1]) ++l;
-        const LevelK k = LK[l];
-        u32x4 q = {0u, 0u, 0u, 0u};
-        if (k.flags == 0u) {
-            const uint32_t r = row - k.base, n = OFF[l + 1] - OFF[l];
-            const uint32_t o[4] = {0u, 1u, k.m1, k.m1 + 1u};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t idx = (r + o[j]) & k.wmask;
-                if (idx < n) q[j] = pack(k.base + idx);
-            }
-        }
-        quads[row] = q;
-    }
+    // (the body is field_common.h's: the march's count launch runs it too)
+    grid_quads_rows<E>(emb, offsets, lv, gridtype, align_corners, rows,
+                       blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, table,
+                       quads);
 }
 
 extern "C" int dfhip_grid_quads(int elem, const float *embeddings, const int32_t *offsets,
@@ -1048,7 +994,7 @@ static int grid_field_backward(
     float *gb1, float *gw2, float *gb2, float *gw3, float *gb3, const int32_t *offsets,
     uint32_t total_rows, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
     float *grad_embeddings, float *grid_partial, uint32_t grid_parts, int accumulate,
-    dfhip_stream_t stream) {
+    dfhip_stream_t stream, float *found_inf = nullptr, bool defer_sum = false) {
     if (!check_field_grid(name, L)) return DFHIP_EINVAL;
     if (!(bound > 0.0f)) {
         set_error("%s: bound must be > 0", name);
@@ -1088,8 +1034,10 @@ static int grid_field_backward(
         mlp_parts = 1;
         (void)hipMemsetAsync(mlp_partial, 0, kParams * sizeof(float), s);
     }
-    k_field_wgrad_sum<<<ceil_div((uint32_t)kParams, 64u), 1024, 0, s>>>(
-        mlp_partial, mlp_parts, gw1, gb1, gw2, gb2, gw3, gb3, accumulate);
+    // defer_sum: the caller sums the partials later (dfhip_param_grad_sums)
+    if (!defer_sum)
+        k_field_wgrad_sum<<<ceil_div((uint32_t)kParams, 64u), 1024, 0, s>>>(
+            mlp_partial, mlp_parts, gw1, gb1, gw2, gb2, gw3, gb3, accumulate, found_inf);
     int rc = check_launch(name);
     if (rc != DFHIP_OK || grad_embeddings == nullptr) return rc;
     if (elem != DFHIP_F16) {
@@ -1144,4 +1092,22 @@ extern "C" int dfhip_grid_field_backward_bf16(
                                d_enc_lbc, mlp_partial, mlp_parts, gw1, gb1, gw2, gb2, gw3, gb3,
                                nullptr, 0, 16, 0.0f, 0, 0, 0, nullptr, nullptr, 0, accumulate,
                                stream);
+}
+
+extern "C" int dfhip_grid_field_backward_check(
+    int elem, const void *enc, const float *xyz, float bound, const float *w1, const float *b1,
+    const float *w2, const float *b2, const float *w3, const float *b3, const float *grad_sigma,
+    const void *grad_rgb, int grad_rgb_dtype, uint32_t cap, const int32_t *m_dev,
+    void *d_enc_lbc, float *mlp_partial, uint32_t mlp_parts, float *gw1, float *gb1, float *gw2,
+    float *gb2, float *gw3, float *gb3, int accumulate, float *found_inf, int defer_sum,
+    dfhip_stream_t stream) {
+    if (elem != DFHIP_F16 && elem != DFHIP_BF16) {
+        set_error("grid_field_backward_check: elem must be f16 or bf16");
+        return DFHIP_EDTYPE;
+    }
+    return grid_field_backward("grid_field_backward_check", elem, enc, xyz, bound, w1, b1, w2, b2,
+                               w3, b3, grad_sigma, grad_rgb, grad_rgb_dtype, cap, m_dev,
+                               d_enc_lbc, mlp_partial, mlp_parts, gw1, gb1, gw2, gb2, gw3, gb3,
+                               nullptr, 0, 16, 0.0f, 0, 0, 0, nullptr, nullptr, 0, accumulate,
+                               stream, found_inf, defer_sum != 0);
 }

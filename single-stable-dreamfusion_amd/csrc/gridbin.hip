@@ -115,6 +115,7 @@ struct Opts {
     uint32_t lane_perm;   // per-segment walk: bit-reversed lane -> run map
     bool clean;           // the counts scratch's totals / plan words are zero on entry
     uint64_t *trace;      // debug walk timeline or null
+    float *found_inf;     // the sum flags a non-finite value it writes (null: no check)
 };
 
 static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
@@ -124,6 +125,7 @@ static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
     r.lane_perm = 1;
     r.clean = false;
     r.trace = nullptr;
+    r.found_inf = nullptr;
     if (!o) return true;
     if (o->walk_mode < -1 || o->walk_mode > 1) {
         set_error("binned backward: walk_mode must be -1, 0 or 1 (got %d)",
@@ -141,6 +143,7 @@ static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
     if (o->lane_perm >= 0) r.lane_perm = o->lane_perm != 0;
     r.clean = o->kept_clean > 0;
     r.trace = o->trace;
+    r.found_inf = o->found_inf;
     return true;
 }
 
@@ -1592,14 +1595,25 @@ __device__ __forceinline__ void clear_totals(const BinInfo &bi, uint32_t *counts
         counts[bi.o_totals + i] = 0u;
 }
 
+// The overflow check of the GradScaler step where the gradient is written
+// (dfhip_binned_opts.found_inf): a workgroup that wrote a non-finite value
+// stores 1.0f, the store opt::k_nonfinite does after re-reading the tensor.
+// found_inf is workgroup-uniform, so every thread reaches the barrier.
+__device__ __forceinline__ void flag_nonfinite(bool bad, float *found_inf) {
+    if (!found_inf) return;
+    if (__syncthreads_or(bad) && threadIdx.x == 0) *found_inf = 1.0f;
+}
+
 // Every (row, channel) of the table sums its bin's P_b images (slots
 // S_b .. S_b + P_b - 1, recorded by k_walk) in order.
 template <typename out_t>
 __global__ __launch_bounds__(256) void k_sum(const float *__restrict__ partial, BinInfo bi,
                                              uint32_t C, uint32_t total_rows,
                                              uint32_t *__restrict__ counts,
-                                             out_t *__restrict__ out, int accumulate) {
+                                             out_t *__restrict__ out, int accumulate,
+                                             float *found_inf) {
     clear_totals(bi, counts);
+    bool bad = false;
     const uint32_t srows = 1u << bi.shift;
     const size_t img = (size_t)srows * C;
     const uint64_t n = (uint64_t)total_rows * C;
@@ -1623,8 +1637,11 @@ __global__ __launch_bounds__(256) void k_sum(const float *__restrict__ partial, 
         }
         for (; p < P; ++p) t += (double)src[(size_t)p * img];
         const float s = accumulate ? (float)out[i] : 0.0f;
-        out[i] = (out_t)(s + (float)t);
+        const out_t w = (out_t)(s + (float)t);
+        bad |= !isfinite((float)w);
+        out[i] = w;
     }
+    flag_nonfinite(bad, found_inf);
 }
 
 // C = 2: one thread per row, both channels as one 8-byte load per image and
@@ -1633,8 +1650,10 @@ template <typename out_t>
 __global__ __launch_bounds__(256) void k_sum2(const float *__restrict__ partial, BinInfo bi,
                                               uint32_t total_rows,
                                               uint32_t *__restrict__ counts,
-                                              out_t *__restrict__ out, int accumulate) {
+                                              out_t *__restrict__ out, int accumulate,
+                                              float *found_inf) {
     clear_totals(bi, counts);
+    bool bad = false;
     const uint32_t srows = 1u << bi.shift;
     const size_t img = (size_t)srows * 2;
     for (uint32_t row = blockIdx.x * blockDim.x + threadIdx.x; row < total_rows;
@@ -1669,9 +1688,12 @@ __global__ __launch_bounds__(256) void k_sum2(const float *__restrict__ partial,
         }
         const float s0 = accumulate ? (float)out[2 * (size_t)row] : 0.0f;
         const float s1 = accumulate ? (float)out[2 * (size_t)row + 1] : 0.0f;
-        out[2 * (size_t)row] = (out_t)(s0 + (float)t0);
-        out[2 * (size_t)row + 1] = (out_t)(s1 + (float)t1);
+        const out_t w0 = (out_t)(s0 + (float)t0), w1 = (out_t)(s1 + (float)t1);
+        bad |= !(isfinite((float)w0) && isfinite((float)w1));
+        out[2 * (size_t)row] = w0;
+        out[2 * (size_t)row + 1] = w1;
     }
+    flag_nonfinite(bad, found_inf);
 }
 
 // Corner-row wrap mode shared by every level (0 mask, 1 modulo, 2 hash; the
@@ -1916,11 +1938,11 @@ static int binned_backward(const char *name, int phase, int grad_dtype, const vo
     if (C == 2) {
         const uint64_t want = ceil_div<uint64_t>((uint64_t)total_rows, 256);
         gb::k_sum2<float><<<(uint32_t)(want < 8192 ? want : 8192), 256, 0, s>>>(
-            partial, bi, total_rows, counts, grad_embeddings, accumulate);
+            partial, bi, total_rows, counts, grad_embeddings, accumulate, op.found_inf);
     } else {
         const uint64_t want = ceil_div<uint64_t>((uint64_t)total_rows * C, 256);
         gb::k_sum<float><<<(uint32_t)(want < 4096 ? want : 4096), 256, 0, s>>>(
-            partial, bi, C, total_rows, counts, grad_embeddings, accumulate);
+            partial, bi, C, total_rows, counts, grad_embeddings, accumulate, op.found_inf);
     }
     return check_launch(name);
 }

@@ -17,6 +17,7 @@
 // values (f32 accumulation), the colour mix is f32.  The writes of pred_rgb
 // channel-major make the reference's reshape/permute/contiguous a no-op.
 #include "common.h"
+#include "field_common.h"
 
 #include <math.h>
 
@@ -352,19 +353,16 @@ __device__ __forceinline__ void entropy_loss_block(uint32_t N, const float *__re
 // With `loss`, one extra (last) block computes the entropy loss of ws — the
 // forward value k_entropy_fwd would give, by the same code — so the native
 // step needs no launch of its own for it.
-__global__ __launch_bounds__(1024) void k_head_wsum(const float *__restrict__ partial,
-                                                    uint32_t blocks, float *gw1, float *gb1,
-                                                    float *gw2, float *gb2,
-                                                    const float *__restrict__ ent_ws = nullptr,
-                                                    uint32_t ent_n = 0, float ent_lambda = 0.0f,
-                                                    float *__restrict__ loss = nullptr) {
-    if (loss && blockIdx.x == gridDim.x - 1) {
-        entropy_loss_block(ent_n, ent_ws, ent_lambda, loss);
-        return;
-    }
+// Block blk of ceil(kParams / 64) of the head's weight-gradient sum (1,024
+// threads).  found_inf (null: off): a workgroup that writes a non-finite
+// value stores 1.0f there (the GradScaler overflow check where the gradient is
+// written).  Every thread returns from here (the caller may have other roles).
+__device__ __forceinline__ void wsum_block(uint32_t blk, const float *__restrict__ partial,
+                                           uint32_t blocks, float *gw1, float *gb1, float *gw2,
+                                           float *gb2, float *found_inf) {
     __shared__ float red[16][64];
     const int o = threadIdx.x & 63, grp = threadIdx.x >> 6;
-    const int p = blockIdx.x * 64 + o;
+    const int p = blk * 64 + o;
     float s = 0.0f;
     if (p < kParams) {
         // rows grp, grp + 16, ... added in that order; eight loads in flight
@@ -380,14 +378,32 @@ __global__ __launch_bounds__(1024) void k_head_wsum(const float *__restrict__ pa
     }
     red[grp][o] = s;
     __syncthreads();
-    if (grp != 0 || p >= kParams) return;
-    s = 0.0f;
+    bool bad = false;
+    if (grp == 0 && p < kParams) {
+        s = 0.0f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) s += red[i][o];
-    if (p < kW1) gw1[p] = s;
-    else if (p < kW1 + kB1) gb1[p - kW1] = s;
-    else if (p < kW1 + kB1 + kW2) gw2[p - kW1 - kB1] = s;
-    else gb2[p - kW1 - kB1 - kW2] = s;
+        for (int i = 0; i < 16; ++i) s += red[i][o];
+        bad = !isfinite(s);
+        if (p < kW1) gw1[p] = s;
+        else if (p < kW1 + kB1) gb1[p - kW1] = s;
+        else if (p < kW1 + kB1 + kW2) gw2[p - kW1 - kB1] = s;
+        else gb2[p - kW1 - kB1 - kW2] = s;
+    }
+    if (found_inf && __syncthreads_or(bad) && threadIdx.x == 0) *found_inf = 1.0f;
+}
+
+__global__ __launch_bounds__(1024) void k_head_wsum(const float *__restrict__ partial,
+                                                    uint32_t blocks, float *gw1, float *gb1,
+                                                    float *gw2, float *gb2,
+                                                    const float *__restrict__ ent_ws = nullptr,
+                                                    uint32_t ent_n = 0, float ent_lambda = 0.0f,
+                                                    float *__restrict__ loss = nullptr,
+                                                    float *found_inf = nullptr) {
+    if (loss && blockIdx.x == gridDim.x - 1) {
+        entropy_loss_block(ent_n, ent_ws, ent_lambda, loss);
+        return;
+    }
+    wsum_block(blockIdx.x, partial, blocks, gw1, gb1, gw2, gb2, found_inf);
 }
 
 // ---------------------------------------------------------------- entropy
@@ -425,6 +441,49 @@ __device__ __forceinline__ void entropy_loss_block(uint32_t N, const float *__re
 __global__ __launch_bounds__(1024) void k_entropy_fwd(uint32_t N, const float *__restrict__ ws,
                                                       float lambda, float *__restrict__ loss) {
     entropy_loss_block(N, ws, lambda, loss);
+}
+
+// The step's parameter-gradient sums in one launch (dfhip_param_grad_sums):
+// workgroups [0, kFieldSumBlocks) are k_field_wgrad_sum's, the next
+// head_blocks k_head_wsum's, one more (loss != null) its entropy-loss block.
+// Each role runs the code of its own launch on its own block index, so the
+// summation orders, and the bits, are those of the separate launches.
+constexpr uint32_t kFieldSumBlocks = (fm::kParams + 63) / 64;
+constexpr uint32_t kHeadSumBlocks = (kParams + 63) / 64;
+
+struct FieldSum {
+    const float *partial;
+    uint32_t parts;
+    float *gw1, *gb1, *gw2, *gb2, *gw3, *gb3;
+    int accumulate;
+};
+struct HeadSum {
+    const float *partial;  // null: no head role
+    uint32_t blocks;
+    float *gw1, *gb1, *gw2, *gb2;
+    const float *ws;
+    uint32_t n;
+    float lambda;
+    float *loss;  // null: no entropy block
+};
+
+__global__ __launch_bounds__(1024) void k_param_grad_sums(FieldSum f, HeadSum h,
+                                                          float *found_inf) {
+    uint32_t b = blockIdx.x;  // the role is workgroup-uniform
+    if (b < kFieldSumBlocks) {
+        fm::wgrad_sum_block(b, f.partial, f.parts, f.gw1, f.gb1, f.gw2, f.gb2, f.gw3, f.gb3,
+                            f.accumulate, found_inf);
+        return;
+    }
+    b -= kFieldSumBlocks;
+    if (h.partial) {
+        if (b < kHeadSumBlocks) {
+            wsum_block(b, h.partial, h.blocks, h.gw1, h.gb1, h.gw2, h.gb2, found_inf);
+            return;
+        }
+        b -= kHeadSumBlocks;
+    }
+    if (h.loss && b == 0) entropy_loss_block(h.n, h.ws, h.lambda, h.loss);
 }
 
 // d loss / d ws = g * lambda / N * log2((1 - a) / a), zero where the clamp is
@@ -483,7 +542,8 @@ static int ray_head_backward(uint32_t N, const float *g_image, const float *ws,
                              float *gw1, float *gb1, float *gw2, float *gb2,
                              const float *ent_grad_loss, float ent_lambda,
                              dfhip_stream_t stream, float *ent_loss = nullptr,
-                             const hd::FwdIO *fwd = nullptr) {
+                             const hd::FwdIO *fwd = nullptr, float *found_inf = nullptr,
+                             bool defer_sum = false) {
     const char *name = "ray_head_backward";
     if (N == 0) return DFHIP_OK;
     if (!g_image || !ws || !grad_image || !grad_ws) {
@@ -507,9 +567,11 @@ static int ray_head_backward(uint32_t N, const float *g_image, const float *ws,
             hd::k_head_bwd_net<false><<<blocks, hd::kThreads, 0, s>>>(
                 N, g_image, ws, rays_d, w1, b1, w2, b2, grad_image, grad_ws, partial,
                 ent_grad_loss, ent_lambda, hd::FwdIO{});
-        hd::k_head_wsum<<<ceil_div((uint32_t)hd::kParams, 64u) + (ent_loss ? 1u : 0u), 1024, 0,
-                          s>>>(partial, blocks, gw1, gb1, gw2, gb2, ws, N, ent_lambda,
-                               ent_loss);
+        // defer_sum: the caller sums the partials later (dfhip_param_grad_sums)
+        if (!defer_sum)
+            hd::k_head_wsum<<<ceil_div((uint32_t)hd::kParams, 64u) + (ent_loss ? 1u : 0u), 1024,
+                              0, s>>>(partial, blocks, gw1, gb1, gw2, gb2, ws, N, ent_lambda,
+                                      ent_loss, found_inf);
     } else {
         hd::k_head_bwd_plain<<<ceil_div(N, 256u), 256, 0, s>>>(N, g_image, ws, bg_color,
                                                                grad_image, grad_ws, grad_bg);
@@ -591,6 +653,77 @@ extern "C" int dfhip_ray_head_forward_backward_entropy_loss(
     return ray_head_backward(N, g_image, ws, rays_d, w1, b1, w2, b2, nullptr, grad_image,
                              grad_ws, nullptr, partial, gw1, gb1, gw2, gb2, grad_loss, lambda,
                              stream, loss, &io);
+}
+
+extern "C" int dfhip_ray_head_backward_check(
+    uint32_t N, const float *g_image, const float *ws, const float *rays_d, const float *w1,
+    const float *b1, const float *w2, const float *b2, const float *bg_color, float *grad_image,
+    float *grad_ws, float *grad_bg, float *partial, float *gw1, float *gb1, float *gw2,
+    float *gb2, const float *grad_loss, float lambda, float *loss, float *found_inf,
+    dfhip_stream_t stream) {
+    if (loss && !grad_loss) {
+        set_error("ray_head_backward_check: the loss needs grad_loss");
+        return DFHIP_EINVAL;
+    }
+    if (N == 0) return loss ? dfhip_entropy_forward(N, ws, lambda, loss, stream) : DFHIP_OK;
+    return ray_head_backward(N, g_image, ws, rays_d, w1, b1, w2, b2, bg_color, grad_image,
+                             grad_ws, grad_bg, partial, gw1, gb1, gw2, gb2, grad_loss, lambda,
+                             stream, loss, nullptr, found_inf);
+}
+
+extern "C" int dfhip_ray_head_forward_backward_entropy_loss_check(
+    uint32_t N, const float *ws, const float *depth, const float *image, const float *rays_d,
+    const float *nears, const float *fars, const float *w1, const float *b1, const float *w2,
+    const float *b2, float *out_image, float *out_depth, uint8_t *mask, const float *g_image,
+    float *grad_image, float *grad_ws, float *partial, float *gw1, float *gb1, float *gw2,
+    float *gb2, const float *grad_loss, float lambda, float *loss, float *found_inf,
+    int defer_sum, dfhip_stream_t stream) {
+    const char *name = "ray_head_forward_backward_entropy_loss_check";
+    if (!loss) {
+        set_error("%s: null loss", name);
+        return DFHIP_EINVAL;
+    }
+    if (N == 0) {
+        set_error("%s: N must be > 0", name);
+        return DFHIP_EINVAL;
+    }
+    if (!w1 || !depth || !image || !nears || !fars || !out_image || !out_depth || !mask ||
+        !grad_loss) {
+        set_error("%s: null pointer (the combined launch needs the background network)", name);
+        return DFHIP_EINVAL;
+    }
+    const hd::FwdIO io{depth, image, nears, fars, out_image, out_depth, mask};
+    return ray_head_backward(N, g_image, ws, rays_d, w1, b1, w2, b2, nullptr, grad_image,
+                             grad_ws, nullptr, partial, gw1, gb1, gw2, gb2, grad_loss, lambda,
+                             stream, loss, &io, found_inf, defer_sum != 0);
+}
+
+extern "C" int dfhip_param_grad_sums(const float *mlp_partial, uint32_t mlp_parts, float *gw1,
+                                     float *gb1, float *gw2, float *gb2, float *gw3, float *gb3,
+                                     int accumulate, uint32_t N, const float *head_partial,
+                                     float *hgw1, float *hgb1, float *hgw2, float *hgb2,
+                                     const float *ws, float lambda, float *loss,
+                                     float *found_inf, dfhip_stream_t stream) {
+    const char *name = "param_grad_sums";
+    if (!mlp_partial || mlp_parts == 0 || !gw1 || !gb1 || !gw2 || !gb2 || !gw3 || !gb3) {
+        set_error("%s: null pointer or no parts in the field role", name);
+        return DFHIP_EINVAL;
+    }
+    if (head_partial && (N == 0 || !hgw1 || !hgb1 || !hgw2 || !hgb2)) {
+        set_error("%s: the head role needs N > 0 and its four gradients", name);
+        return DFHIP_EINVAL;
+    }
+    if ((ws != nullptr) != (loss != nullptr)) {
+        set_error("%s: the entropy role needs both ws and loss", name);
+        return DFHIP_EINVAL;
+    }
+    const hd::FieldSum f{mlp_partial, mlp_parts, gw1, gb1, gw2, gb2, gw3, gb3, accumulate};
+    const hd::HeadSum h{head_partial, ceil_div(N, (uint32_t)hd::kRays), hgw1, hgb1, hgw2, hgb2,
+                        ws, N, lambda, loss};
+    const uint32_t blocks = hd::kFieldSumBlocks + (head_partial ? hd::kHeadSumBlocks : 0u) +
+                            (loss ? 1u : 0u);
+    hd::k_param_grad_sums<<<blocks, 1024, 0, as_stream(stream)>>>(f, h, found_inf);
+    return check_launch(name);
 }
 
 extern "C" int dfhip_entropy_forward(uint32_t N, const float *ws, float lambda, float *loss,

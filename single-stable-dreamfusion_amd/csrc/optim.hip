@@ -31,6 +31,11 @@
 //   3. k_finalize: step += 1 per tensor unless found_inf, then
 //      torch._amp_update_scale_ (backoff 0.5 on inf, x2 after 2000 clean
 //      steps).
+// The replayed train step (dfhip_adam_amp_step_tail) skips 1. for the tensors
+// whose writers already reported a non-finite value they wrote (no launch when
+// that is all of them), and its 3. also stores the step's live sample count.
+// 3. as the work of 2.'s last workgroup or wave to finish (a ticket counter
+// instead of a launch) was measured and not kept: DESIGN.md, round 7.
 // The per-tensor descriptors (pointers, sizes, group hyper-parameters) travel
 // by value; the scale, growth tracker, found_inf and step counters are the
 // torch GradScaler / Adam state tensors themselves, so checkpoints keep the
@@ -188,10 +193,27 @@ __device__ __forceinline__ void finalize_wave(const Batch &B, bool inf, float *s
     *found_inf = 0.0f;  // every lane read it above; the wave runs in lock step
 }
 
+// The live sample count of a replayed train step (the march's counter), stored
+// into the model's step_counter row by the finalize: the row index is a device
+// word the step's prologue wrote.  All null: nothing is stored.
+struct Live {
+    const int32_t *count;  // {samples, rays}
+    int32_t *rows;         // [rows][2]
+    const int32_t *row;    // device word: this step's row
+};
+
 __global__ __launch_bounds__(64) void k_finalize(Batch B, float *scale, int32_t *growth_tracker,
                                                  float *found_inf, float growth_factor,
-                                                 float backoff_factor, int growth_interval) {
+                                                 float backoff_factor, int growth_interval,
+                                                 Live live) {
     if (blockIdx.x != 0) return;
+    // a lane finalize_wave leaves idle (at most kMaxTensors lanes bump a step)
+    static_assert(kMaxTensors <= 63, "lane 63 is free");
+    if (threadIdx.x == 63 && live.count) {
+        const size_t row = (size_t)live.row[0];
+        live.rows[2 * row] = live.count[0];
+        live.rows[2 * row + 1] = live.count[1];
+    }
     finalize_wave(B, *found_inf != 0.0f, scale, growth_tracker, found_inf, growth_factor,
                   backoff_factor, growth_interval);
 }
@@ -204,15 +226,27 @@ using namespace dfhip;
 namespace dfhip {
 namespace opt {
 
+struct TailArgs {
+    uint32_t covered_mask;
+    const int32_t *live;
+    int32_t *live_rows;
+    const int32_t *live_row;
+};
+
 static int adam_amp_step(int count, float *const *params, const float *const *grads,
                          float *const *exp_avg, float *const *exp_avg_sq, float *const *steps,
                          const uint64_t *numel, const float *lr, const int32_t *lr_slot,
                          const float *lr_dev, const float *beta1, const float *beta2,
                          const float *eps, const float *weight_decay, float *scale,
                          int32_t *growth_tracker, float *found_inf, float growth_factor,
-                         float backoff_factor, int growth_interval, hipStream_t s) {
-    const char *name = "adam_amp_step";
+                         float backoff_factor, int growth_interval, hipStream_t s,
+                         const TailArgs *tail = nullptr) {
+    const char *name = tail ? "adam_amp_step_tail" : "adam_amp_step";
     if (count <= 0) return DFHIP_OK;
+    if (tail && tail->live && (!tail->live_rows || !tail->live_row)) {
+        set_error("%s: a live count without its rows / row word", name);
+        return DFHIP_EINVAL;
+    }
     if (count > kMaxTensors) {
         set_error("%s: at most %d tensors (got %d)", name, kMaxTensors, count);
         return DFHIP_EINVAL;
@@ -262,10 +296,33 @@ static int adam_amp_step(int count, float *const *params, const float *const *gr
     }
     B.blocks = blocks;
     if (blocks == 0) blocks = 1;  // all tensors empty: one block that finds no work
+    if (tail) {
+        // the re-reading check over the tensors no writer covered: a batch of
+        // their own (only p / g / n / block0 are read), no launch when empty
+        Batch U;
+        U.count = 0;
+        U.blocks = 0;
+        U.lr_dev = nullptr;
+        for (int k = 0; k < count; ++k) {
+            if ((tail->covered_mask >> k) & 1u) continue;
+            const uint32_t nb = (k + 1 < count ? B.t[k + 1].block0 : B.blocks) - B.t[k].block0;
+            if (nb == 0) continue;
+            Tensor &u = U.t[U.count++];
+            u = B.t[k];
+            u.block0 = U.blocks;
+            U.blocks += nb;
+        }
+        if (U.blocks) k_nonfinite<<<U.blocks, kThreads, 0, s>>>(U, found_inf);
+        k_adam<<<blocks, kThreads, 0, s>>>(B, scale, found_inf);
+        k_finalize<<<1, 64, 0, s>>>(B, scale, growth_tracker, found_inf, growth_factor,
+                                    backoff_factor, growth_interval,
+                                    Live{tail->live, tail->live_rows, tail->live_row});
+        return check_launch(name);
+    }
     k_nonfinite<<<blocks, kThreads, 0, s>>>(B, found_inf);
     k_adam<<<blocks, kThreads, 0, s>>>(B, scale, found_inf);
     k_finalize<<<1, 64, 0, s>>>(B, scale, growth_tracker, found_inf, growth_factor,
-                                backoff_factor, growth_interval);
+                                backoff_factor, growth_interval, Live{nullptr, nullptr, nullptr});
     return check_launch(name);
 }
 
@@ -308,4 +365,28 @@ extern "C" int dfhip_adam_amp_step_lr_dev(int count, float *const *params,
                               lr_slot, lr_dev, beta1, beta2, eps, weight_decay, scale,
                               growth_tracker, found_inf, growth_factor, backoff_factor,
                               growth_interval, as_stream(stream));
+}
+
+extern "C" int dfhip_adam_amp_step_tail(int count, float *const *params,
+                                        const float *const *grads, float *const *exp_avg,
+                                        float *const *exp_avg_sq, float *const *steps,
+                                        const uint64_t *numel, const int32_t *lr_slot,
+                                        const float *lr_dev, const float *beta1,
+                                        const float *beta2, const float *eps,
+                                        const float *weight_decay, float *scale,
+                                        int32_t *growth_tracker, float *found_inf,
+                                        float growth_factor, float backoff_factor,
+                                        int growth_interval, uint32_t covered_mask,
+                                        const int32_t *live, int32_t *live_rows,
+                                        const int32_t *live_row,
+                                        dfhip_stream_t stream) {
+    if (count > 0 && (!lr_slot || !lr_dev)) {
+        set_error("adam_amp_step_tail: null lr slot array or device lr");
+        return DFHIP_EINVAL;
+    }
+    const opt::TailArgs tail{covered_mask, live, live_rows, live_row};
+    return opt::adam_amp_step(count, params, grads, exp_avg, exp_avg_sq, steps, numel, nullptr,
+                              lr_slot, lr_dev, beta1, beta2, eps, weight_decay, scale,
+                              growth_tracker, found_inf, growth_factor, backoff_factor,
+                              growth_interval, as_stream(stream), &tail);
 }

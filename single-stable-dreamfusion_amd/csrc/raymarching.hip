@@ -19,6 +19,7 @@
 //  * No N*max_steps zero-fill: the emit pass zeroes only the align tail.
 //  * One wave per workgroup for the per-ray compositing kernels: 16k rays =
 //    256 workgroups = one per CU, instead of 64 CUs with 256-thread blocks.
+#include "field_common.h"
 #include "march_common.h"
 
 #include <type_traits>
@@ -145,13 +146,13 @@ constexpr uint32_t kStageFloats = 5;  // x, y, z, dt, dl of a staged sample
 // Pass 1 (raymarching.cu:341-400): count occupied samples per ray.
 // STAGE: also keep each sample (x, y, z, dt, dl as f32) at row n * max_steps + i
 // of `stage`, so the emit pass copies instead of marching again.
-template <typename scalar_t, bool STAGE = false>
-__global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_count(
+template <typename scalar_t, bool STAGE>
+__device__ __forceinline__ void march_count_block(
     const scalar_t *__restrict__ rays_o, const scalar_t *__restrict__ rays_d,
-    const uint8_t *__restrict__ grid, MarchConsts k, uint32_t max_steps, uint32_t N,
+    const uint8_t *__restrict__ grid, const MarchConsts &k, uint32_t max_steps, uint32_t N,
     const scalar_t *__restrict__ nears, const scalar_t *__restrict__ fars,
     int32_t *rays, int32_t *counter, const scalar_t *__restrict__ noises,
-    int32_t *block_sums, float *__restrict__ stage = nullptr) {
+    int32_t *block_sums, float *__restrict__ stage) {
     __shared__ int s_cnt[kMarchRaysPerBlock];
     const uint32_t w = threadIdx.x >> 6;
     const uint32_t n = blockIdx.x * kMarchRaysPerBlock + w;
@@ -188,6 +189,53 @@ __global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_count(
         atomicAdd(counter, tot);
         atomicAdd(counter + 1, (int)min(kMarchRaysPerBlock, N - blockIdx.x * kMarchRaysPerBlock));
     }
+}
+
+template <typename scalar_t, bool STAGE = false>
+__global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_count(
+    const scalar_t *__restrict__ rays_o, const scalar_t *__restrict__ rays_d,
+    const uint8_t *__restrict__ grid, MarchConsts k, uint32_t max_steps, uint32_t N,
+    const scalar_t *__restrict__ nears, const scalar_t *__restrict__ fars,
+    int32_t *rays, int32_t *counter, const scalar_t *__restrict__ noises,
+    int32_t *block_sums, float *__restrict__ stage = nullptr) {
+    march_count_block<scalar_t, STAGE>(rays_o, rays_d, grid, k, max_steps, N, nears, fars, rays,
+                                       counter, noises, block_sums, stage);
+}
+
+// The staged count pass with a second role: the workgroups past the march's
+// own (blockIdx.x >= march_blocks) build the field's f16 / bf16 table copy and
+// its corner quads (fm::grid_quads_rows, what k_grid_quads runs).  The march
+// leaves most of the device idle while its longest rays finish, and the quads
+// depend on the parameters alone, so the stream rides in that tail instead of
+// a launch of its own between the emit and the field forward.  The riders are
+// the LAST workgroups, dispatched when the march's have all started.  Neither
+// role reads what the other writes.
+struct QuadRider {
+    const float *emb;
+    const int32_t *offsets;
+    ge::Levels lv;
+    uint32_t gridtype;
+    int align_corners;
+    uint32_t rows;
+    uint32_t *table;
+    fm::u32x4 *quads;
+};
+
+template <typename scalar_t, typename E>
+__global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_count_quads(
+    const scalar_t *__restrict__ rays_o, const scalar_t *__restrict__ rays_d,
+    const uint8_t *__restrict__ grid, MarchConsts k, uint32_t max_steps, uint32_t N,
+    const scalar_t *__restrict__ nears, const scalar_t *__restrict__ fars,
+    int32_t *rays, int32_t *counter, const scalar_t *__restrict__ noises,
+    int32_t *block_sums, float *__restrict__ stage, uint32_t march_blocks, QuadRider q) {
+    if (blockIdx.x >= march_blocks) {  // workgroup-uniform
+        fm::grid_quads_rows<E>(q.emb, q.offsets, q.lv, q.gridtype, q.align_corners, q.rows,
+                               (blockIdx.x - march_blocks) * blockDim.x + threadIdx.x,
+                               (gridDim.x - march_blocks) * blockDim.x, q.table, q.quads);
+        return;
+    }
+    march_count_block<scalar_t, true>(rays_o, rays_d, grid, k, max_steps, N, nears, fars, rays,
+                                      counter, noises, block_sums, stage);
 }
 
 template <typename scalar_t>
@@ -858,6 +906,59 @@ extern "C" int dfhip_march_rays_train_count_staged(
             (const scalar_t *)nears, (const scalar_t *)fars, rays, counter,
             (const scalar_t *)noises, block_sums, stage)));
     return check_launch("march_rays_train_count_staged");
+}
+
+extern "C" int dfhip_march_rays_train_count_staged_quads(
+    int dtype, const void *rays_o, const void *rays_d, const uint8_t *grid, float bound,
+    float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, const void *nears,
+    const void *fars, int32_t *rays, int32_t *counter, const void *noises, int32_t *block_sums,
+    float *stage, int elem, const float *embeddings, const int32_t *offsets, uint32_t L,
+    float S, uint32_t Hb, uint32_t gridtype, int align_corners, uint32_t rows, void *table,
+    void *quads, dfhip_stream_t stream) {
+    const char *name = "march_rays_train_count_staged_quads";
+    if (!march_args_ok(name, C, H, max_steps)) return DFHIP_EINVAL;
+    if (dtype != DFHIP_F32) {
+        set_error("%s: f32 rays only", name);
+        return DFHIP_EDTYPE;
+    }
+    if (L != (uint32_t)fm::kLevels) {
+        set_error("%s: the field's grid has %d levels (got %u)", name, fm::kLevels, L);
+        return DFHIP_EINVAL;
+    }
+    if (N == 0 || rows == 0) {
+        set_error("%s: N and rows must be > 0", name);
+        return DFHIP_EINVAL;
+    }
+    if (!stage || !embeddings || !offsets || !table || !quads) {
+        set_error("%s: null pointer", name);
+        return DFHIP_EINVAL;
+    }
+    if (((uintptr_t)quads & 15u) != 0) {
+        set_error("%s: quads must be 16-byte aligned", name);
+        return DFHIP_EINVAL;
+    }
+    const MarchConsts k = make_consts(bound, dt_gamma, max_steps, C, H);
+    const QuadRider q{embeddings, offsets, ge::make_levels(L, S, Hb), gridtype, align_corners,
+                      rows, (uint32_t *)table, (fm::u32x4 *)quads};
+    const uint32_t threads = 64 * kMarchRaysPerBlock;
+    const uint32_t march_blocks = ceil_div(N, kMarchRaysPerBlock);
+    // one row per rider thread, grid-stride past four workgroups per CU
+    const uint32_t want = ceil_div(rows, threads), cap = 4u * device_cus();
+    const uint32_t riders = want < cap ? want : cap;
+    hipStream_t s = as_stream(stream);
+#define DFHIP_COUNT_QUADS(E)                                                                   \
+    k_march_train_count_quads<float, E><<<march_blocks + riders, threads, 0, s>>>(            \
+        (const float *)rays_o, (const float *)rays_d, grid, k, max_steps, N,                   \
+        (const float *)nears, (const float *)fars, rays, counter, (const float *)noises,       \
+        block_sums, stage, march_blocks, q)
+    if (elem == DFHIP_F16) DFHIP_COUNT_QUADS(half_t);
+    else if (elem == DFHIP_BF16) DFHIP_COUNT_QUADS(bf16_t);
+    else {
+        set_error("%s: elem must be f16 or bf16", name);
+        return DFHIP_EDTYPE;
+    }
+#undef DFHIP_COUNT_QUADS
+    return check_launch(name);
 }
 
 extern "C" int dfhip_march_rays_train_emit_staged(

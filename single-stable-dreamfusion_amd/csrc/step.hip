@@ -72,6 +72,10 @@ struct Args {
     float lr[kMaxLr];
     uint32_t n_lr;
     float *lr_dev;
+    // the step_counter row of this step, for the launch that stores the live
+    // sample count at the end of the replayed graph (null: not written)
+    uint32_t row;
+    int32_t *row_dev;
 };
 
 __global__ __launch_bounds__(256) void k_step_prologue(Args a, float *__restrict__ rays_o,
@@ -88,6 +92,7 @@ __global__ __launch_bounds__(256) void k_step_prologue(Args a, float *__restrict
         counter[0] = 0;
         counter[1] = 0;
     }
+    if (n == 0 && a.row_dev) a.row_dev[0] = (int32_t)a.row;
     if (n < a.n_lr) a.lr_dev[n] = a.lr[n];
     if (n >= N) return;
     float o[3], d[3];
@@ -135,12 +140,13 @@ __global__ __launch_bounds__(256) void k_step_prologue(Args a, float *__restrict
 
 using namespace dfhip;
 
-extern "C" int dfhip_train_step_prologue_lr(
+extern "C" int dfhip_train_step_prologue_row(
     const float *pose, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
     const float *aabb, float min_near, uint64_t seed, uint64_t step, int perturb,
     const float *alphas, uint32_t min_step, uint32_t max_step, float *rays_o, float *rays_d,
     float *nears, float *fars, float *noises, float *bg_color, float *g_image, int32_t *counter,
-    const float *lr_host, uint32_t n_lr, float *lr_dev, dfhip_stream_t stream) {
+    const float *lr_host, uint32_t n_lr, float *lr_dev, uint32_t row, int32_t *row_dev,
+    dfhip_stream_t stream) {
     const char *name = "train_step_prologue";
     if (!pose || !aabb || !rays_o || !rays_d || !nears || !fars) {
         set_error("%s: null pointer", name);
@@ -178,6 +184,8 @@ extern "C" int dfhip_train_step_prologue_lr(
     a.max_step = max_step;
     a.n_lr = n_lr;
     a.lr_dev = lr_dev;
+    a.row = row;
+    a.row_dev = row_dev;
     for (uint32_t i = 0; i < st::kMaxLr; ++i) a.lr[i] = i < n_lr ? lr_host[i] : 0.0f;
     // at least one block: the counter reset and the lr pack run with no rays
     const uint32_t blocks = n ? ceil_div((uint32_t)n, 256u) : 1u;
@@ -185,6 +193,18 @@ extern "C" int dfhip_train_step_prologue_lr(
                                                                 noises, bg_color, g_image,
                                                                 counter);
     return check_launch(name);
+}
+
+extern "C" int dfhip_train_step_prologue_lr(
+    const float *pose, float fx, float fy, float cx, float cy, uint32_t H, uint32_t W,
+    const float *aabb, float min_near, uint64_t seed, uint64_t step, int perturb,
+    const float *alphas, uint32_t min_step, uint32_t max_step, float *rays_o, float *rays_d,
+    float *nears, float *fars, float *noises, float *bg_color, float *g_image, int32_t *counter,
+    const float *lr_host, uint32_t n_lr, float *lr_dev, dfhip_stream_t stream) {
+    return dfhip_train_step_prologue_row(pose, fx, fy, cx, cy, H, W, aabb, min_near, seed, step,
+                                         perturb, alphas, min_step, max_step, rays_o, rays_d,
+                                         nears, fars, noises, bg_color, g_image, counter,
+                                         lr_host, n_lr, lr_dev, 0, nullptr, stream);
 }
 
 extern "C" int dfhip_train_step_prologue(const float *pose, float fx, float fy, float cx,

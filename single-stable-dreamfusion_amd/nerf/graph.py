@@ -86,7 +86,7 @@ class GraphedTrainStep:
             if t.world_size == 1 or collective:
                 adam = t.native_adam()
                 if adam:
-                    nat.attach_optimizer(adam)
+                    nat.attach_optimizer(adam, data_parallel=collective)
                     if collective:
                         nat.attach_allreduce(t.world_size)
                     self.optimizer_in_graph = True
@@ -102,6 +102,9 @@ class GraphedTrainStep:
                 # pair their collectives step for step.
                 nat.body()
                 nat.embedding_backward()
+                # the dry run's gradient writers may have raised the overflow
+                # flag, and no optimizer tail ran to clear it
+                nat.clear_found_inf()
             with torch.cuda.graph(self.graph, stream=self.stream):
                 self.loss = nat.body()
                 nat.embedding_backward()
@@ -167,13 +170,16 @@ class GraphedTrainStep:
                 g = self.deferred[0][1]
             self.grads.append((p, g))
 
-    def load(self, data, text_z):
+    def load(self, data, text_z, row=0):
         """This step's camera rays (made straight into the graph's input buffers
-        from a host pose when the batch has one) and prompt embedding."""
+        from a host pose when the batch has one) and prompt embedding.  row:
+        the model.step_counter row a native step that stores its live sample
+        count itself (stores_live_count()) writes it to."""
         if self.native is not None:
             t = self.trainer
             self.native.prologue(data["pose"], data["intrinsics"],
-                                 int(t.opt.seed) * 1000003 + int(t.local_rank), t.global_step)
+                                 int(t.opt.seed) * 1000003 + int(t.local_rank), t.global_step,
+                                 row=row)
             return
         if "pose" in data and "rays_o" not in data:
             from .utils import get_rays_host_pose
@@ -195,6 +201,14 @@ class GraphedTrainStep:
             launch()
         for p, g in self.grads:
             p.grad = g
+
+    def stores_live_count(self):
+        """True when the step's last launch (the optimizer's finalize, in the graph)
+        stores the march's counter into row `row` of model.step_counter, so the
+        Trainer needs no copy after the replay."""
+        nat = self.native
+        return (nat is not None and self.optimizer_in_graph and nat.stores_live_count
+                and nat.live_rows is self.trainer.model.step_counter)
 
     def step_timed(self):
         """The native step's launches run eagerly (no graph) under whatever

@@ -22,6 +22,16 @@ the step is, with the same kernels and the same arithmetic:
       data-parallel: the graph ends at the embedding gradient, and the
       all-reduce and Adam follow eagerly)
 
+Small launches of this sequence are folded into their neighbours, each
+behind a Trainer switch (default on) and bit-identical to the separate
+launches (tests/test_gpu_step_tail.py): the table copy and its corner quads
+ride in the march's count launch (quads_in_march); the field's and the
+head's weight-gradient sums and the entropy loss are one launch after the
+field backward (merged_grad_sums); the sums that write parameter gradients
+report a non-finite value themselves, so the optimizer launches no check
+(fold_overflow_check); the optimizer's finalize stores the live sample count
+into model.step_counter (store_live_count).
+
 Every launch sits in a _dfhip.timed region with its algorithmic bytes (the
 regions are no-ops unless a kernel timer is installed, and the graph is
 captured without one): bench.py's kernel-timing pass runs the same body
@@ -244,12 +254,47 @@ class NativeAlbedoStep:
         self.adam = None
         self._lr_source = None
         self.n_params = sum(p.numel() for p in self.params)
+        # the folded tail (attach_optimizer): the flag the gradient writers
+        # report a non-finite value to, and the step_counter row (a device
+        # word the prologue writes) the last launch stores the live count into
+        self.found_inf = None
+        self.row_dev = torch.zeros(1, **i32)
+        self.stores_live_count = False
+        self.live_rows = None
+        # the table copy and corner quads ride in the march's count launch
+        self.quads_in_march = bool(getattr(trainer, "quads_in_march", True))
+        # one launch for the field's and the head's weight-gradient sums and
+        # the entropy loss (the albedo one-pass step with the combined head)
+        self.merged_sums = (bool(getattr(trainer, "merged_grad_sums", True))
+                            and not self.two_pass and not self.shade_code)
 
-    def attach_optimizer(self, native_adam):
+    def attach_optimizer(self, native_adam, data_parallel=False):
         """Run GradScaler + Adam (nerf/optim.py NativeAdamAmp) as the step's
-        last launches, with device learning rates (captured in the graph)."""
-        self.adam = native_adam.device_lr_launch(self.lr_dev)
+        last launches, with device learning rates (captured in the graph).
+
+        trainer.fold_overflow_check: the writers of the embedding, field and
+        background-network gradients report non-finite values themselves and
+        the optimizer launches no check of its own (not with data_parallel:
+        the check must see the reduced gradients); trainer.store_live_count:
+        the finalize launch stores the sample count into model.step_counter
+        (both: dfhip_adam_amp_step_tail)."""
+        t = self.trainer
         self._lr_source = native_adam.group_lrs
+        tail = {}
+        fold = bool(getattr(t, "fold_overflow_check", True)) and not data_parallel
+        if fold:
+            covered = [self.encoder.embeddings] + list(self.mlp)
+            if self.bg_layers is not None:
+                covered += self._bg_weights()
+            tail["covered"] = covered
+        if getattr(t, "store_live_count", True):
+            self.live_rows = t.model.step_counter
+            tail.update(live=self.counter, live_rows=self.live_rows, live_row=self.row_dev)
+            self.stores_live_count = True
+        self.adam = native_adam.device_lr_launch(self.lr_dev, tail=tail or None)
+        if fold:
+            self.found_inf = native_adam.found_inf
+            self._emb_launch = self._emb_launch2 = None  # rebuilt with the flag in their opts
 
     def attach_allreduce(self, world_size, group=None):
         """Make the step's tail the data-parallel exchange: ONE in-place
@@ -272,9 +317,10 @@ class NativeAlbedoStep:
             self.adam()
 
     # ------------------------------------------------------------ per step
-    def prologue(self, pose, intrinsics, seed, step):
+    def prologue(self, pose, intrinsics, seed, step, row=0):
         """Rays, near/far, noise, the SDS gradient and counter reset from the
-        host pose [4, 4] (or [1, 4, 4]) of this step (one eager launch)."""
+        host pose [4, 4] (or [1, 4, 4]) of this step (one eager launch).  row:
+        the model.step_counter row of this step (stores_live_count)."""
         host = np.ascontiguousarray(np.asarray(pose, dtype=np.float32).reshape(-1, 4, 4)[0, :3, :4])
         fx, fy, cx, cy = (float(v) for v in intrinsics)
         lo, hi = self.t_range
@@ -283,12 +329,12 @@ class NativeAlbedoStep:
         N = self.N
         with _dfhip.timed("step_prologue", N * (24 + 8 + 4 + 12) +
                           (12 * N if self.bg_color is not None else 0)):
-            call("dfhip_train_step_prologue_lr", host.ctypes.data, fx, fy, cx, cy, self.H,
+            call("dfhip_train_step_prologue_row", host.ctypes.data, fx, fy, cx, cy, self.H,
                  self.W, self.aabb.ctypes.data, 0.2, int(seed) & 0xFFFFFFFFFFFFFFFF,
                  int(step) & 0xFFFFFFFFFFFFFFFF, 1, ptr(self.alphas), lo, hi, ptr(self.rays_o),
                  ptr(self.rays_d), ptr(self.nears), ptr(self.fars), ptr(self.noises),
                  ptr(self.bg_color), ptr(self.g_image), ptr(self.counter), lr_host, len(lrs),
-                 ptr(self.lr_dev), stream())
+                 ptr(self.lr_dev), int(row), ptr(self.row_dev), stream())
         if self.shade_code:
             # the light direction (renderer.py:462-464), same (seed, step) key
             call("dfhip_shading_light", ptr(self.rays_o), int(seed) & 0xFFFFFFFFFFFFFFFF,
@@ -314,11 +360,20 @@ class NativeAlbedoStep:
         # march (raymarching.py:161-235, device count): rays + near/far +
         # noise + bitfield in, (ray, offset, count) + one 20-B stage row per
         # sample out; the emit copies the stage into xyz / dir / delta rows
-        with T("march_rays_train_count", 48 * N + (m.density_bitfield.numel()), md, 20):
-            _raymarching.march_rays_train_count_staged(
-                self.rays_o, self.rays_d, m.density_bitfield, m.bound, self.dt_gamma,
-                self.max_steps, N, m.cascade, m.grid_size, self.nears, self.fars, self.rays,
-                self.counter, self.noises, self.block_sums, self.stage)
+        march_args = (self.rays_o, self.rays_d, m.density_bitfield, m.bound, self.dt_gamma,
+                      self.max_steps, N, m.cascade, m.grid_size, self.nears, self.fars, self.rays,
+                      self.counter, self.noises, self.block_sums, self.stage)
+        if self.quads_in_march:
+            # the table copy and the quads by the launch's last workgroups,
+            # in the tail of the march's longest rays (no launch of their own)
+            with T("march_rays_train_count", 48 * N + (m.density_bitfield.numel()) +
+                   rc * (4 + hb) + 16 * self.rows, md, 20):
+                _raymarching.march_rays_train_count_staged_quads(
+                    *march_args, self.encoder.embeddings.detach(), self.encoder.offsets, S, Hb,
+                    gridtype, align, self.table, self.quads)
+        else:
+            with T("march_rays_train_count", 48 * N + (m.density_bitfield.numel()), md, 20):
+                _raymarching.march_rays_train_count_staged(*march_args)
         # per-sample directions only for the shadings (the albedo step reads
         # rays_d per ray): 12 B per sample fewer written
         dirs = self.dirs if self.shade_code else None
@@ -329,7 +384,8 @@ class NativeAlbedoStep:
         # field (grid.py:38-39 autocast table, network_grid.py:76-87); with a
         # shading, the six finite-difference stencil points of every sample are
         # field rows too (network_grid.py:90-114)
-        quads()
+        if not self.quads_in_march:
+            quads()
         if self.shade_code:
             with T("shading_stencil", 0, md, 12 + 84):
                 call("dfhip_shading_stencil", ptr(self.xyzs), ptr(self.m_dev), cap, FD_EPS,
@@ -361,6 +417,9 @@ class NativeAlbedoStep:
         # of its backward launch (the recomputed background, bit-identical)
         combined = (not self.two_pass and self.lam > 0 and bw[0] is not None
                     and bool(getattr(self.trainer, "combined_head", True)))
+        fi = self.found_inf  # the folded overflow check's flag, or None
+        # the head's weight sum and the entropy loss wait for the field's sum
+        defer = combined and self.merged_sums
         if not combined:
             with T("ray_head_forward", 60 * N):
                 call("dfhip_ray_head_forward", N, ptr(self.ws), ptr(self.depth), ptr(self.image),
@@ -380,13 +439,25 @@ class NativeAlbedoStep:
                      ptr(self.bg_color), ptr(self.grad_image), ptr(self.grad_ws), None,
                      ptr(self.head_partial), *[ptr(g) for g in gbw])
         with T("ray_head_backward", 60 * N if not combined else 120 * N):
-            if combined:
+            if combined and (fi is not None or defer):
+                call("dfhip_ray_head_forward_backward_entropy_loss_check", N, ptr(self.ws),
+                     ptr(self.depth), ptr(self.image), ptr(self.rays_d), ptr(self.nears),
+                     ptr(self.fars), *[ptr(w) for w in bw], ptr(self.out_image),
+                     ptr(self.out_depth), ptr(self.mask), ptr(self.g_image), ptr(self.grad_image),
+                     ptr(self.grad_ws), ptr(self.head_partial), *[ptr(g) for g in gbw],
+                     ptr(scale), self.lam, ptr(self.loss), ptr(fi), int(defer), stream())
+            elif combined:
                 call("dfhip_ray_head_forward_backward_entropy_loss", N, ptr(self.ws),
                      ptr(self.depth), ptr(self.image), ptr(self.rays_d), ptr(self.nears),
                      ptr(self.fars), *[ptr(w) for w in bw], ptr(self.out_image),
                      ptr(self.out_depth), ptr(self.mask), ptr(self.g_image), ptr(self.grad_image),
                      ptr(self.grad_ws), ptr(self.head_partial), *[ptr(g) for g in gbw],
                      ptr(scale), self.lam, ptr(self.loss), stream())
+            elif fi is not None and bw[0] is not None:
+                # (the entropy gradient and loss as below, when lambda > 0)
+                call("dfhip_ray_head_backward_check", *head_args,
+                     ptr(scale) if self.lam > 0 else None, self.lam,
+                     ptr(self.loss) if self.lam > 0 else None, ptr(fi), stream())
             elif self.lam > 0:
                 # head backward + the entropy term's gradient (upstream: the
                 # scale); the entropy loss itself (utils.py:386-391) comes out
@@ -418,7 +489,18 @@ class NativeAlbedoStep:
                 self.enc, self.xyz_field, m.bound, self.mlp, self.grad_sigma_field,
                 self.grad_albedo, self.d_enc, self.mlp_partial, [p.grad for p in self.mlp],
                 self.encoder.offsets, self.rows, S, Hb, gridtype, align, None, None,
-                _parts(self.rows, self.C), self.m_field)
+                _parts(self.rows, self.C), self.m_field, found_inf=fi,
+                defer_sum=self.merged_sums)
+            if self.merged_sums:
+                # one launch: the field's sum, the head's (deferred above) and
+                # the entropy loss, each in its own fixed order
+                call("dfhip_param_grad_sums", ptr(self.mlp_partial),
+                     _fieldmlp.backward_parts(self.fcap) if self.fcap else 1,
+                     *[ptr(p.grad) for p in self.mlp], 0, N,
+                     ptr(self.head_partial) if defer else None,
+                     *[ptr(g) if defer else None for g in gbw],
+                     ptr(self.ws) if defer else None, self.lam,
+                     ptr(self.loss) if defer else None, ptr(fi), stream())
         return self.loss
 
     def _backward_two_pass(self, bw, scale):
@@ -430,9 +512,16 @@ class NativeAlbedoStep:
         S, Hb, gridtype, align, _ = self.meta
         from gridencoder.grid import _parts
         gbw = self._bg_grads()
-        call("dfhip_ray_head_backward", N, ptr(self.g_image), ptr(self.ws), ptr(self.rays_d),
-             *[ptr(w) for w in bw], ptr(self.bg_color), ptr(self.grad_image), ptr(self.grad_ws),
-             None, ptr(self.head_partial), *[ptr(g) for g in gbw], stream())
+        if self.found_inf is not None and bw[0] is not None:
+            call("dfhip_ray_head_backward_check", N, ptr(self.g_image), ptr(self.ws),
+                 ptr(self.rays_d), *[ptr(w) for w in bw], ptr(self.bg_color),
+                 ptr(self.grad_image), ptr(self.grad_ws), None, ptr(self.head_partial),
+                 *[ptr(g) for g in gbw], None, 0.0, None, ptr(self.found_inf), stream())
+        else:
+            call("dfhip_ray_head_backward", N, ptr(self.g_image), ptr(self.ws), ptr(self.rays_d),
+                 *[ptr(w) for w in bw], ptr(self.bg_color), ptr(self.grad_image),
+                 ptr(self.grad_ws), None, ptr(self.head_partial), *[ptr(g) for g in gbw],
+                 stream())
         passes = [(self.grad_ws, self.grad_image, self.grad_sigma, self.grad_albedo, self.d_enc,
                    False)]
         if self.lam > 0:
@@ -449,7 +538,7 @@ class NativeAlbedoStep:
                 self.enc, self.xyzs, m.bound, self.mlp, g_sig, g_alb, d_enc,
                 self.mlp_partial, [p.grad for p in self.mlp], self.encoder.offsets, self.rows, S,
                 Hb, gridtype, align, None, None, _parts(self.rows, self.C), self.m_dev,
-                accumulate=acc)
+                accumulate=acc, found_inf=self.found_inf)
 
     def embedding_backward(self):
         """Binned embedding-gradient scatter (eager, timed like the autograd
@@ -492,11 +581,19 @@ class NativeAlbedoStep:
         kw["opts"] = self._kept_clean_opts()
         self._emb_launch = _gridencoder.binned_launcher(*args, **kw)
 
+    def clear_found_inf(self):
+        """Zero the overflow flag after launches that ran the checking writers
+        without the optimizer tail that clears it (the capture's dry run)."""
+        if self.found_inf is not None:
+            self.found_inf.zero_()
+
     def _kept_clean_opts(self):
         """The call's BinnedOpts (self.binned_opts or the defaults) with
         kept_clean set: the persistent counts scratch needs no fill launch."""
         o = self.binned_opts if self.binned_opts is not None else _gridencoder.BinnedOpts()
         o.kept_clean = 1 if getattr(self.trainer, "kept_clean_scratch", True) else 0
+        # the sum reports a non-finite gradient it writes (folded overflow check)
+        o.found_inf = ptr(self.found_inf)
         return o
 
     def time_field(self, reps=5):

@@ -58,6 +58,7 @@ class NativeAdamAmp:
         self._unit = None  # (scale 1.0, growth tracker) when the scaler is disabled
         self._ptr_key = None
         self._arrays = None
+        self._tensors = []
 
     def _state(self, p):
         st = self.optimizer.state[p]
@@ -121,7 +122,7 @@ class NativeAdamAmp:
         """Current learning rate of every param group (host floats)."""
         return [float(g["lr"]) for g in self.optimizer.param_groups]
 
-    def device_lr_launch(self, lr_dev):
+    def device_lr_launch(self, lr_dev, tail=None):
         """The step as a closure over device-resident learning rates (tensor k
         reads lr_dev[its group]): captured once in the native train step's
         HIP graph (nerf/graph.py), while the prologue launch writes lr_dev
@@ -129,7 +130,14 @@ class NativeAdamAmp:
         buffers and optimizer state, like step()'s fast path.  By design the
         closure (and the graph that captured it) holds the groups' betas, eps
         and weight_decay by value: unlike step(), which re-reads them, a later
-        change of those needs a new device_lr_launch and a new capture."""
+        change of those needs a new device_lr_launch and a new capture.
+
+        tail (dict, optional): the replayed step's form, dfhip_adam_amp_step_tail.
+        "covered": parameters whose gradient writers already stored a
+        non-finite value they wrote into self.found_inf (the re-reading check
+        skips them); "live" / "live_rows" / "live_row": the int32 sample
+        counter [2], the [rows, 2] table it is stored into and the device word
+        holding the row.  Same update, bit for bit."""
         sc = self.scaler
         if sc.is_enabled():
             if sc._scale is None:
@@ -156,6 +164,29 @@ class NativeAdamAmp:
         fn = _dfhip.load().dfhip_adam_amp_step_lr_dev
         found_inf, opt = self.found_inf, self.optimizer
         keep = (slots, self._arrays, lr_dev, scale, tracker, found_inf)
+        if tail is not None:
+            # the replayed step's tail (dfhip_adam_amp_step_tail): the overflow
+            # check only over the gradients whose writers did not make it, the
+            # live sample count stored by the finalize launch
+            covered = {id(p) for p in tail.get("covered", ())}
+            mask = sum(1 << k for k, p in enumerate(self._tensors) if id(p) in covered)
+            live, rows, row = tail.get("live"), tail.get("live_rows"), tail.get("live_row")
+            fn_tail = _dfhip.load().dfhip_adam_amp_step_tail
+            keep += (live, rows, row)
+            ptr = _dfhip.ptr
+
+            def launch_tail():
+                rc = fn_tail(n, P, G, M, V, S, N, slots, lr_dev.data_ptr(), B1, B2, E, WD,
+                             scale.data_ptr(), tracker.data_ptr(), found_inf.data_ptr(),
+                             float(growth), float(backoff), int(interval), mask, ptr(live),
+                             ptr(rows), ptr(row), _dfhip.stream())
+                if rc != 0:
+                    raise RuntimeError(f"dfhip_adam_amp_step_tail failed ({rc}): "
+                                       f"{_dfhip.load().dfhip_last_error().decode()}")
+                opt._opt_called = True
+            launch_tail.keep = keep
+            launch_tail.covered_mask = mask
+            return launch_tail
 
         def launch():
             rc = fn(n, P, G, M, V, S, N, slots, lr_dev.data_ptr(), B1, B2, E, WD,
@@ -186,6 +217,7 @@ class NativeAdamAmp:
                 ts.append((p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["step"], gi, b1, b2,
                            g["eps"], g["weight_decay"]))
         self._ptr_key = key
+        self._tensors = [t[0] for t in ts]  # the parameter of descriptor k
         if not ts:
             self._arrays = None
             return

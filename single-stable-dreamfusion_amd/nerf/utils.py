@@ -316,6 +316,22 @@ class Trainer(object):
         # native steps with the injected SDS gradient: the ray head's forward
         # and backward as one launch (dfhip_ray_head_forward_backward_entropy_loss)
         self.combined_head = True
+        # native steps with the optimizer in the graph (one GPU): the tail's
+        # small launches folded (results bit-identical either way)
+        #  - the GradScaler overflow check made where each gradient is written
+        #    instead of a pass that re-reads them all (data-parallel steps keep
+        #    the pass: it must see the reduced gradients)
+        self.fold_overflow_check = True
+        #  - the field's and the head's weight-gradient sums (and the entropy
+        #    loss) as one launch after the field backward (albedo, one pass)
+        self.merged_grad_sums = True
+        #  - the live sample count stored into model.step_counter by the step's
+        #    last launch (the optimizer's finalize) instead of a
+        #    device-to-device copy after each replay
+        self.store_live_count = True
+        #  - the table copy and corner quads built by extra workgroups of the
+        #    march's count launch
+        self.quads_in_march = True
         # graph-replayed steps through the reference-API modules (no native
         # step, model.fused_field False): the host-count march, then a graph
         # per sample-count bucket (nerf/graph.py BucketedModuleStep)
@@ -627,12 +643,13 @@ class Trainer(object):
             self._graphs[key] = g
         else:
             model.local_step += 1
-        g.load(data, text_z)
+        g.load(data, text_z, row=row)
         if self.step_hook is not None:
             self.step_hook(g)  # bench.py kernel timing: the eager twin of the replay
         else:
             g.replay()
-        model.step_counter[row].copy_(g.counter)
+        if not g.stores_live_count():  # else the step's last launch stored it
+            model.step_counter[row].copy_(g.counter)
         self.optimizer_step(stepped=g.optimizer_in_graph)
         return g.loss
 
