@@ -1113,6 +1113,69 @@ int dfhip_raster_uv_interp(const float *vt, const int32_t *ft, const float *v, c
 int dfhip_texture_dilate(const uint8_t *src_rgb, const uint8_t *src_mask, uint32_t H, uint32_t W,
                          uint8_t *dst_rgb, uint8_t *dst_mask, dfhip_stream_t stream);
 
+/* ---- hierarchical sampling of NeRFRenderer.run (csrc/hiersample.hip) ---------
+ * The torch glue of the renderer without --cuda_ray (nerf/renderer.py:301-443)
+ * between its field calls.  One wave per ray; all buffers f32 except `rgbs`
+ * and its gradient (`dtype`: DFHIP_F32 or DFHIP_F16).  T = num_steps,
+ * t = upsample_steps: 3 <= T <= 256, t <= 256, T + t <= 512, else
+ * DFHIP_EINVAL.  Rays [N, 3], aabb [6], nears / fars [N].
+ *
+ * dfhip_uniform_samples (renderer.py:331-343): lin [T] = linspace(0, 1, T),
+ *   noise [N, T] uniform draws or NULL (no perturbation) -> z [N, T] and the
+ *   positions rays_o + rays_d z clamped into aabb, xyzs [N, T, 3]; the
+ *   operations in the reference's order, uncontracted. */
+int dfhip_uniform_samples(const float *rays_o, const float *rays_d, const float *aabb,
+                          const float *nears, const float *fars, const float *lin,
+                          const float *noise, uint32_t N, uint32_t T, float *z, float *xyzs,
+                          dfhip_stream_t stream);
+/* renderer.py:358-370 with sample_pdf (renderer.py:15-49): the coarse z [N, T]
+ *   and sigma [N, T] -> deltas (sample_dist = (far - near) / T after the last),
+ *   alphas, transmittance as the running product of (1 - alpha) + 1e-15,
+ *   weights, the pdf of weights[1:-1] + 1e-5 over the midpoints, and for each
+ *   u [N, t] (NULL: the deterministic (j + 0.5) / t) the bin found with
+ *   right=True, span < 1e-5 -> 1, and the interpolated depth -> new_z [N, t]
+ *   and its clamped positions new_xyzs [N, t, 3].  t = 0 is a no-op. */
+int dfhip_importance_samples(const float *rays_o, const float *rays_d, const float *aabb,
+                             const float *nears, const float *fars, const float *z,
+                             const float *sigma, const float *u, uint32_t N, uint32_t T,
+                             uint32_t t, float *new_z, float *new_xyzs, dfhip_stream_t stream);
+/* renderer.py:379-387 (torch.sort of the concatenated depths and the gathers):
+ *   z_all [N, T + t] ascending, order [N, T + t] the index of each entry in the
+ *   concatenation [z, new_z], xyzs_all [N, T + t, 3] the positions in that
+ *   order.  Equal depths (-0 = +0) keep their concatenation order, so the
+ *   result is a repeatable permutation. */
+int dfhip_merge_samples(const float *z, const float *new_z, const float *xyzs,
+                        const float *new_xyzs, uint32_t N, uint32_t T, uint32_t t, float *z_all,
+                        int32_t *order, float *xyzs_all, dfhip_stream_t stream);
+/* renderer.py:389-393, 414-421: sigma of sorted sample i is sigma_coarse
+ *   [N, T] or sigma_new [N, t] at order[i] (a permutation of 0 .. T + t - 1 per
+ *   ray; NULL with t = 0: the identity), dz from z_all [N, T + t] with
+ *   sample_dist [N] after the last, alpha = 1 - exp(-dz sigma), T_i the product
+ *   of (1 - alpha_j) + 1e-15 over j < i, w = alpha T -> weights [N, T + t],
+ *   weights_sum [N], depth [N] = sum w clamp((z - near) / (far - near), 0, 1)
+ *   (NaN where near = far, as the reference) and image [N, 3] = sum w rgbs
+ *   (before the background mix), rgbs [N, T + t, 3] in sorted order. */
+int dfhip_composite_uniform_forward(int dtype, const float *sigma_coarse, const float *sigma_new,
+                                    const int32_t *order, const float *z_all, const float *nears,
+                                    const float *fars, const float *sample_dist, const void *rgbs,
+                                    uint32_t N, uint32_t T, uint32_t t, float *weights_sum,
+                                    float *depth, float *image, float *weights,
+                                    dfhip_stream_t stream);
+/* Its backward in closed form (the reference differentiates the cumprod):
+ *   grad_weights_sum [N], grad_depth [N], grad_image [N, 3], each NULL when
+ *   that output took no part in the loss (its term is then left out; a zero
+ *   grad_depth would make NaN of a ray with near = far) -> grad_sigma_coarse
+ *   [N, T] and grad_sigma_new [N, t], scattered back through order, and
+ *   grad_rgbs [N, T + t, 3] in the type of rgbs (NULL: not wanted). */
+int dfhip_composite_uniform_backward(int dtype, const float *grad_weights_sum,
+                                     const float *grad_depth, const float *grad_image,
+                                     const float *sigma_coarse, const float *sigma_new,
+                                     const int32_t *order, const float *z_all, const float *nears,
+                                     const float *fars, const float *sample_dist,
+                                     const void *rgbs, uint32_t N, uint32_t T, uint32_t t,
+                                     float *grad_sigma_coarse, float *grad_sigma_new,
+                                     void *grad_rgbs, dfhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,14 @@ _SIGS = {
     "dfhip_raster_uv_interp": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp,
                                _vp],
     "dfhip_texture_dilate": [_vp, _vp, _u32, _u32, _vp, _vp, _vp],
+    "dfhip_uniform_samples": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp],
+    "dfhip_importance_samples": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp,
+                                 _vp, _vp],
+    "dfhip_merge_samples": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp],
+    "dfhip_composite_uniform_forward": [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
+                                        _u32, _vp, _vp, _vp, _vp, _vp],
+    "dfhip_composite_uniform_backward": [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

@@ -232,3 +232,87 @@ def composite_rays(n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, 
         checked(t, w)
     call("dfhip_composite_rays", dt, n_alive, n_step, T_thresh, ptr(rays_alive), ptr(rays_t),
          ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(weights), ptr(depth), ptr(image), stream())
+
+
+# ---- hierarchical sampling of NeRFRenderer.run (csrc/hiersample.hip, native)
+
+def _f32_opt(t, what):
+    if t is not None:
+        _f32_only(t, what)
+
+
+def _i32_opt(t, what):
+    if t is not None:
+        checked(t, what, "int")
+
+
+def uniform_samples(rays_o, rays_d, aabb, nears, fars, lin, noise, N, T, z, xyzs):
+    for t, w in ((rays_o, "rays_o"), (rays_d, "rays_d"), (aabb, "aabb"), (nears, "nears"),
+                 (fars, "fars"), (lin, "lin"), (z, "z"), (xyzs, "xyzs")):
+        _f32_only(t, w)
+    _f32_opt(noise, "noise")
+    call("dfhip_uniform_samples", ptr(rays_o), ptr(rays_d), ptr(aabb), ptr(nears), ptr(fars),
+         ptr(lin), ptr(noise), N, T, ptr(z), ptr(xyzs), stream())
+
+
+def importance_samples(rays_o, rays_d, aabb, nears, fars, z, sigma, u, N, T, t, new_z, new_xyzs):
+    for a, w in ((rays_o, "rays_o"), (rays_d, "rays_d"), (aabb, "aabb"), (nears, "nears"),
+                 (fars, "fars"), (z, "z"), (sigma, "sigma"), (new_z, "new_z"),
+                 (new_xyzs, "new_xyzs")):
+        _f32_only(a, w)
+    _f32_opt(u, "u")
+    call("dfhip_importance_samples", ptr(rays_o), ptr(rays_d), ptr(aabb), ptr(nears), ptr(fars),
+         ptr(z), ptr(sigma), ptr(u), N, T, t, ptr(new_z), ptr(new_xyzs), stream())
+
+
+def merge_samples(z, new_z, xyzs, new_xyzs, N, T, t, z_all, order, xyzs_all):
+    for a, w in ((z, "z"), (new_z, "new_z"), (xyzs, "xyzs"), (new_xyzs, "new_xyzs"),
+                 (z_all, "z_all"), (xyzs_all, "xyzs_all")):
+        _f32_only(a, w)
+    checked(order, "order", "int")
+    call("dfhip_merge_samples", ptr(z), ptr(new_z), ptr(xyzs), ptr(new_xyzs), N, T, t, ptr(z_all),
+         ptr(order), ptr(xyzs_all), stream())
+
+
+def _rgbs_code(rgbs, what):
+    checked(rgbs, what)
+    if rgbs.dtype not in (torch.float32, torch.float16):
+        raise RuntimeError(f"{what} must be a float32 or float16 tensor")
+    return _d.dtype_code(rgbs, what)
+
+
+def composite_uniform_forward(sigma_coarse, sigma_new, order, z_all, nears, fars, sample_dist, rgbs,
+                              N, T, t, weights_sum, depth, image, weights):
+    for a, w in ((sigma_coarse, "sigma_coarse"), (z_all, "z_all"), (nears, "nears"),
+                 (fars, "fars"), (sample_dist, "sample_dist"), (weights_sum, "weights_sum"),
+                 (depth, "depth"), (image, "image"), (weights, "weights")):
+        _f32_only(a, w)
+    _f32_opt(sigma_new, "sigma_new")
+    _i32_opt(order, "order")
+    rd = _rgbs_code(rgbs, "rgbs")
+    call("dfhip_composite_uniform_forward", rd, ptr(sigma_coarse), ptr(sigma_new), ptr(order),
+         ptr(z_all), ptr(nears), ptr(fars), ptr(sample_dist), ptr(rgbs), N, T, t,
+         ptr(weights_sum), ptr(depth), ptr(image), ptr(weights), stream())
+
+
+def composite_uniform_backward(grad_weights_sum, grad_depth, grad_image, sigma_coarse, sigma_new,
+                               order, z_all, nears, fars, sample_dist, rgbs, N, T, t,
+                               grad_sigma_coarse, grad_sigma_new, grad_rgbs):
+    for a, w in ((sigma_coarse, "sigma_coarse"), (z_all, "z_all"), (nears, "nears"),
+                 (fars, "fars"), (sample_dist, "sample_dist"),
+                 (grad_sigma_coarse, "grad_sigma_coarse")):
+        _f32_only(a, w)
+    for a, w in ((grad_weights_sum, "grad_weights_sum"), (grad_depth, "grad_depth"),
+                 (grad_image, "grad_image"), (sigma_new, "sigma_new"),
+                 (grad_sigma_new, "grad_sigma_new")):
+        _f32_opt(a, w)
+    _i32_opt(order, "order")
+    rd = _rgbs_code(rgbs, "rgbs")
+    if grad_rgbs is not None:
+        checked(grad_rgbs, "grad_rgbs")
+        if grad_rgbs.dtype != rgbs.dtype:
+            raise RuntimeError("grad_rgbs must have the dtype of rgbs")
+    call("dfhip_composite_uniform_backward", rd, ptr(grad_weights_sum), ptr(grad_depth),
+         ptr(grad_image), ptr(sigma_coarse), ptr(sigma_new), ptr(order), ptr(z_all), ptr(nears),
+         ptr(fars), ptr(sample_dist), ptr(rgbs), N, T, t, ptr(grad_sigma_coarse),
+         ptr(grad_sigma_new), ptr(grad_rgbs), stream())

@@ -97,6 +97,10 @@ class NeRFRenderer(nn.Module):
         # eval frames: the background net runs on a side stream beside the
         # fused render (bit-identical; False: after it, in the head)
         self.infer_overlap_bg = True
+        # run(): the sampling / sorting / compositing between the field calls as
+        # native kernels (csrc/hiersample.hip; False: the reference's torch ops)
+        self.native_run = True
+        self.native_run_calls = self.torch_run_calls = 0
         # generator of the density-grid jitter (None: torch's default)
         self.grid_generator = None
         # (nears, fars, xyzs, dirs, deltas, rays) of a march already run for
@@ -169,8 +173,10 @@ class NeRFRenderer(nn.Module):
     # ------------------------------------------------------------------ run()
     def run(self, rays_o, rays_d, num_steps=128, upsample_steps=128, light_d=None,
             ambient_ratio=1.0, shading="albedo", bg_color=None, perturb=False, **kwargs):
-        """Coarse (uniform) + importance sampled rendering in plain torch
-        (reference renderer.py:301-443).  rays_o, rays_d: [B, N, 3]."""
+        """Coarse (uniform) + importance sampled rendering (reference
+        renderer.py:301-443): the glue between the field calls as native
+        kernels (_run_native) when `native_run` is set and the sizes allow,
+        else in plain torch.  rays_o, rays_d: [B, N, 3]."""
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)
@@ -180,6 +186,12 @@ class NeRFRenderer(nn.Module):
         aabb = self.aabb_train if self.training else self.aabb_infer
 
         nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
+        if self.native_run and self._run_native_eligible(rays_o, rays_d, nears, num_steps,
+                                                         upsample_steps):
+            return self._run_native(rays_o, rays_d, aabb, nears, fars, prefix, num_steps,
+                                    upsample_steps, light_d, ambient_ratio, shading, bg_color,
+                                    perturb)
+        self.torch_run_calls += 1
         nears = nears.unsqueeze(-1)
         fars = fars.unsqueeze(-1)
         if light_d is None:
@@ -240,6 +252,71 @@ class NeRFRenderer(nn.Module):
         image = torch.sum(weights.unsqueeze(-1) * rgbs, dim=-2)
         image = image + (1 - weights_sum).unsqueeze(-1) * self._bg(rays_d, bg_color)
 
+        results["image"] = image.view(*prefix, 3)
+        results["depth"] = depth.view(*prefix)
+        results["weights_sum"] = weights_sum
+        results["mask"] = (nears < fars).reshape(*prefix)
+        return results
+
+    @staticmethod
+    def _run_native_eligible(rays_o, rays_d, nears, num_steps, upsample_steps):
+        """The sizes and tensors csrc/hiersample.hip serves: f32 rays on the
+        GPU, 3 <= T <= 256, t <= 256, T + t <= 512; anything else keeps torch."""
+        return (rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32
+                and nears.dtype == torch.float32 and 3 <= num_steps <= 256
+                and 0 <= upsample_steps <= 256 and num_steps + upsample_steps <= 512)
+
+    def _linspace(self, num_steps, device):
+        """linspace(0, 1, T) of run(), made by torch once per (T, device)."""
+        cache = self.__dict__.setdefault("_run_linspace", {})
+        key = (num_steps, device)
+        if key not in cache:
+            cache[key] = torch.linspace(0.0, 1.0, num_steps, device=device)
+        return cache[key]
+
+    def _run_native(self, rays_o, rays_d, aabb, nears, fars, prefix, num_steps, upsample_steps,
+                    light_d, ambient_ratio, shading, bg_color, perturb):
+        """run() with its torch glue as four kernels and one autograd node
+        (raymarching.uniform_samples / importance_samples / merge_samples /
+        composite_uniform).  The field calls, their order and every random draw
+        (order, shape) are those of the torch path below."""
+        self.native_run_calls += 1
+        N = rays_o.shape[0]
+        device = rays_o.device
+        results = {}
+        if light_d is None:
+            light_d = safe_normalize(rays_o[0] + torch.randn(3, device=device, dtype=torch.float))
+
+        noise = torch.rand((N, num_steps), device=device) if perturb else None
+        z, xyzs = raymarching.uniform_samples(rays_o, rays_d, aabb, nears, fars,
+                                              self._linspace(num_steps, device), noise)
+        sigma = self.density(xyzs.reshape(-1, 3))["sigma"].view(N, num_steps).float()
+        new_sigma = order = None
+        if upsample_steps > 0:
+            u = torch.rand([N, upsample_steps], device=device) if self.training else None
+            new_z, new_xyzs = raymarching.importance_samples(rays_o, rays_d, aabb, nears, fars, z,
+                                                             sigma, upsample_steps, u)
+            new_sigma = self.density(new_xyzs.reshape(-1, 3))["sigma"].view(N, upsample_steps)
+            new_sigma = new_sigma.float()
+            z, order, xyzs = raymarching.merge_samples(z, new_z, xyzs, new_xyzs)
+
+        dirs = rays_d.view(-1, 1, 3).expand_as(xyzs)
+        _, rgbs, normals = self(xyzs.reshape(-1, 3), dirs.reshape(-1, 3), light_d,
+                                ratio=ambient_ratio, shading=shading)
+        rgbs = rgbs.view(N, -1, 3)
+        if rgbs.dtype not in (torch.float32, torch.float16):
+            rgbs = rgbs.float()
+        sample_dist = (fars - nears) / num_steps
+        weights_sum, depth, image, weights = raymarching.composite_uniform(
+            sigma, new_sigma, order, z, nears, fars, sample_dist, rgbs)
+        if normals is not None:
+            normals = normals.view(N, -1, 3)
+            orient = weights * (normals * dirs).sum(-1).clamp(min=0) ** 2
+            results["loss_orient"] = orient.sum(-1).mean()
+            jitter = self.normal(xyzs + torch.randn_like(xyzs) * 1e-2).view(N, -1, 3)
+            results["loss_smooth"] = (normals - jitter).abs().mean()
+
+        image = image + (1 - weights_sum).unsqueeze(-1) * self._bg(rays_d, bg_color)
         results["image"] = image.view(*prefix, 3)
         results["depth"] = depth.view(*prefix)
         results["weights_sum"] = weights_sum

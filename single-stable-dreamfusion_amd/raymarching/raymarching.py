@@ -409,3 +409,120 @@ class _composite_rays(Function):
 
 
 composite_rays = _composite_rays.apply
+
+
+# ----------------------------------------------------------------------------
+# hierarchical sampling of NeRFRenderer.run (reference nerf/renderer.py:15-49,
+# 331-421, plain torch there; csrc/hiersample.hip here)
+# ----------------------------------------------------------------------------
+
+def _ray_operands(rays_o, rays_d, aabb, nears, fars):
+    rays_o, rays_d = _flat3(rays_o), _flat3(rays_d)
+    n = rays_o.shape[0]
+    return (rays_o, rays_d, aabb.contiguous(), nears.contiguous().view(n),
+            fars.contiguous().view(n), n)
+
+
+@torch.no_grad()
+def uniform_samples(rays_o, rays_d, aabb, nears, fars, lin, noise=None):
+    """The coarse samples of run(): z = nears + (fars - nears) * lin, jittered by
+    (noise - 0.5) * (fars - nears) / T when `noise` [N, T] (uniform draws) is
+    given, and the positions rays_o + rays_d * z clamped into aabb, bit-equal
+    to the torch expressions.  lin: linspace(0, 1, T) on the device.
+    Returns z [N, T], xyzs [N, T, 3] (float32)."""
+    rays_o, rays_d, aabb, nears, fars, n = _ray_operands(rays_o, rays_d, aabb, nears, fars)
+    T = lin.shape[0]
+    z = torch.empty(n, T, dtype=torch.float32, device=rays_o.device)
+    xyzs = torch.empty(n, T, 3, dtype=torch.float32, device=rays_o.device)
+    _backend.uniform_samples(rays_o, rays_d, aabb, nears, fars, lin.contiguous(),
+                             None if noise is None else noise.contiguous(), n, T, z, xyzs)
+    return z, xyzs
+
+
+@torch.no_grad()
+def importance_samples(rays_o, rays_d, aabb, nears, fars, z, sigma, n_samples, u=None):
+    """sample_pdf over the coarse samples' weights: z, sigma [N, T] -> `n_samples`
+    new depths per ray, one for each uniform draw of u [N, n_samples] (None:
+    the deterministic (j + 0.5) / n_samples), and their clamped positions.
+    Returns new_z [N, t], new_xyzs [N, t, 3]."""
+    rays_o, rays_d, aabb, nears, fars, n = _ray_operands(rays_o, rays_d, aabb, nears, fars)
+    T, t = z.shape[1], int(n_samples)
+    if u is not None and tuple(u.shape) != (n, t):
+        raise RuntimeError(f"u must be [{n}, {t}], got {tuple(u.shape)}")
+    new_z = torch.empty(n, t, dtype=torch.float32, device=rays_o.device)
+    new_xyzs = torch.empty(n, t, 3, dtype=torch.float32, device=rays_o.device)
+    _backend.importance_samples(rays_o, rays_d, aabb, nears, fars, z.contiguous(),
+                                sigma.detach().contiguous().view(n, T),
+                                None if u is None else u.contiguous(), n, T, t, new_z, new_xyzs)
+    return new_z, new_xyzs
+
+
+@torch.no_grad()
+def merge_samples(z, new_z, xyzs, new_xyzs):
+    """Sort the union of the coarse and the new samples by depth: z_all
+    [N, T + t] ascending, order [N, T + t] (int32 indices into cat([z, new_z],
+    1); equal depths in concatenation order) and the positions in that order."""
+    n, T, t = z.shape[0], z.shape[1], new_z.shape[1]
+    dev = z.device
+    z_all = torch.empty(n, T + t, dtype=torch.float32, device=dev)
+    order = torch.empty(n, T + t, dtype=torch.int32, device=dev)
+    xyzs_all = torch.empty(n, T + t, 3, dtype=torch.float32, device=dev)
+    _backend.merge_samples(z.contiguous(), new_z.contiguous(), xyzs.contiguous(),
+                           new_xyzs.contiguous(), n, T, t, z_all, order, xyzs_all)
+    return z_all, order, xyzs_all
+
+
+class _composite_uniform(Function):
+    @staticmethod
+    @custom_fwd(device_type="cuda")
+    def forward(ctx, sigma_coarse, sigma_new, order, z_all, nears, fars, sample_dist, rgbs):
+        """Compositing of run(): sigma_coarse [N, T] and sigma_new [N, t] (None
+        with t = 0) are read through order [N, T + t] (None: the identity),
+        rgbs [N, T + t, 3] (float32 or float16) is in sorted order.  Returns
+        weights_sum [N], depth [N], image [N, 3] (before the background mix)
+        and weights [N, T + t] (not differentiable).  The backward is the closed
+        form of the cumulative product; an output that took no part in the loss
+        contributes no term (a ray that misses the box has a NaN depth, and a
+        zero gradient times it would be NaN)."""
+        n, T = sigma_coarse.shape
+        t = 0 if sigma_new is None else sigma_new.shape[1]
+        sigma_coarse = sigma_coarse.contiguous()
+        sigma_new = None if t == 0 else sigma_new.contiguous()
+        order = None if t == 0 else order.contiguous()
+        z_all, rgbs = z_all.contiguous(), rgbs.contiguous()
+        nears, fars = nears.contiguous().view(n), fars.contiguous().view(n)
+        sample_dist = sample_dist.contiguous().view(n)
+        opts = dict(dtype=torch.float32, device=sigma_coarse.device)
+        weights_sum = torch.empty(n, **opts)
+        depth = torch.empty(n, **opts)
+        image = torch.empty(n, 3, **opts)
+        weights = torch.empty(n, T + t, **opts)
+        _backend.composite_uniform_forward(sigma_coarse, sigma_new, order, z_all, nears, fars,
+                                           sample_dist, rgbs, n, T, t, weights_sum, depth, image,
+                                           weights)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(weights)
+        ctx.save_for_backward(sigma_coarse, sigma_new, order, z_all, nears, fars, sample_dist, rgbs)
+        ctx.dims = (n, T, t)
+        return weights_sum, depth, image, weights
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad_weights_sum, grad_depth, grad_image, grad_weights):
+        sigma_coarse, sigma_new, order, z_all, nears, fars, sample_dist, rgbs = ctx.saved_tensors
+        n, T, t = ctx.dims
+        if grad_weights_sum is None and grad_depth is None and grad_image is None:
+            return (None,) * 8
+        grads = [None if g is None else g.float().contiguous()
+                 for g in (grad_weights_sum, grad_depth, grad_image)]
+        grad_sigma_coarse = torch.empty_like(sigma_coarse)
+        grad_sigma_new = None if t == 0 else torch.empty_like(sigma_new)
+        want_rgbs = ctx.needs_input_grad[7] and grads[2] is not None
+        grad_rgbs = torch.empty_like(rgbs) if want_rgbs else None
+        _backend.composite_uniform_backward(*grads, sigma_coarse, sigma_new, order, z_all, nears,
+                                            fars, sample_dist, rgbs, n, T, t, grad_sigma_coarse,
+                                            grad_sigma_new, grad_rgbs)
+        return grad_sigma_coarse, grad_sigma_new, None, None, None, None, None, grad_rgbs
+
+
+composite_uniform = _composite_uniform.apply
