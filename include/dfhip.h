@@ -831,6 +831,33 @@ int dfhip_ray_head_forward_backward_entropy_loss_check(
     float *gb2, const float *grad_loss, float lambda, float *loss, float *found_inf,
     int defer_sum, dfhip_stream_t stream);
 
+/* The per-ray chain of the native albedo train step as ONE launch:
+ * dfhip_composite_rays_train_forward_mixed, then
+ * dfhip_ray_head_forward_backward_entropy_loss_check, then
+ * dfhip_composite_rays_train_backward_mixed with zero_tail = 0, on the same
+ * arguments (their union; M is the sample capacity: a ray with offset + num >
+ * M counts as empty and its zero fill is clipped to M).  Every buffer the
+ * three entries write is written and every value is bit-identical to theirs:
+ * ws / depth / image [N], out_image [3,N] / out_depth / mask, grad_image /
+ * grad_ws, `partial` (dfhip_ray_head_partial_floats(N) floats, the same
+ * per-workgroup partials), grad_sigmas [M] / grad_rgbs [M,3], and with
+ * defer_sum = 0 gw1 / gb1 / gw2 / gb2, loss and found_inf from the weight-sum
+ * launch that follows (defer_sum != 0: none of those; the caller runs
+ * dfhip_param_grad_sums).  rgbs / grad_rgbs are rgb_dtype (DFHIP_F32, _F16 or
+ * _BF16), everything else f32.  N > 0; only found_inf may be NULL.
+ * Precondition: rays[3 n] == n for every ray (the records of the staged
+ * march), so ray n's per-ray rows are row n; the records live on the device,
+ * so this is not checked. */
+int dfhip_ray_chain_train(
+    int rgb_dtype, const float *sigmas, const void *rgbs, const float *deltas,
+    const int32_t *rays, uint32_t M, uint32_t N, float T_thresh, float *ws, float *depth,
+    float *image, const float *rays_d, const float *nears, const float *fars, const float *w1,
+    const float *b1, const float *w2, const float *b2, float *out_image, float *out_depth,
+    uint8_t *mask, const float *g_image, float *grad_image, float *grad_ws, float *partial,
+    float *gw1, float *gb1, float *gw2, float *gb2, const float *grad_loss, float lambda,
+    float *loss, float *found_inf, int defer_sum, float *grad_sigmas, void *grad_rgbs,
+    dfhip_stream_t stream);
+
 /* nerf/utils.py:386-391 entropy regulariser: loss[0] = lambda * mean(-a log2 a
  * - (1 - a) log2(1 - a)), a = clamp(ws, 1e-5, 1 - 1e-5) (f64 sum); backward
  * grad_ws = grad_loss[0] * lambda / N * log2((1 - a) / a) where the clamp

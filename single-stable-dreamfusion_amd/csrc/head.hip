@@ -17,6 +17,7 @@
 // values (f32 accumulation), the colour mix is f32.  The writes of pred_rgb
 // channel-major make the reference's reshape/permute/contiguous a no-op.
 #include "common.h"
+#include "chain_common.h"
 #include "field_common.h"
 
 #include <math.h>
@@ -244,6 +245,12 @@ struct FwdIO {
     uint8_t *mask;
 };
 
+__device__ __forceinline__ void write_partials(const float (&s_x)[kRays][kIn + 1],
+                                               const half_t (&s_dh)[kRays][kHid],
+                                               const half_t (&s_h)[kRays][kHid],
+                                               const float (&s_do)[kRays][4],
+                                               float *__restrict__ partial);
+
 // Network backward: the forward is recomputed (kSub = 16 lanes per ray), then the
 // sigmoid and the two f16 Linear layers are run backward and this block's
 // weight-gradient partials (f32 sums over its 64 rays of f16 products) formed
@@ -324,6 +331,16 @@ __global__ __launch_bounds__(kThreads) void k_head_bwd_net(
 #pragma unroll
         for (int k = 0; k < kOut; ++k) s_do[r][k] = dout[k];
     __syncthreads();
+    write_partials(s_x, s_dh, s_h, s_do, partial);
+}
+
+// This workgroup's weight-gradient partials from the LDS images of its 64
+// rays (after a barrier): f32 sums in ray order.
+__device__ __forceinline__ void write_partials(const float (&s_x)[kRays][kIn + 1],
+                                               const half_t (&s_dh)[kRays][kHid],
+                                               const half_t (&s_h)[kRays][kHid],
+                                               const float (&s_do)[kRays][4],
+                                               float *__restrict__ partial) {
     float *out = partial + (size_t)blockIdx.x * kParams;
     for (int p = threadIdx.x; p < kParams; p += blockDim.x) {
         float s = 0.0f;
@@ -343,6 +360,230 @@ __global__ __launch_bounds__(kThreads) void k_head_bwd_net(
         out[p] = s;
     }
 }
+
+// ------------------------------------------------------------ fused ray chain
+// k_composite_train_fwd_w -> k_head_bwd_net<true> -> k_composite_train_bwd_w<DENSE>
+// as ONE launch (dfhip_ray_chain_train): the three kernels already give a ray
+// sixteen consecutive lanes, the head's upstream gradient is an input (it does
+// not depend on pred_rgb), and the compositing backward needs only this ray's
+// ws / image and the head's grad_ws / grad_image, which stay in registers.
+// Workgroups are the head's (64 rays, 1,024 threads), so the weight-gradient
+// partials keep their membership and order; every buffer the three launches
+// write is written, with the same expressions in the same order (bit-identical).
+// Precondition: rays[3 n] == n (the staged march's records), so ray n's
+// per-ray rows are row n.
+struct RayChainArgs {
+    const float *sigmas;
+    const void *rgbs;
+    const float *deltas;
+    const int32_t *rays;
+    uint32_t M, N;
+    float T_thresh;
+    float *ws, *depth, *image;
+    const float *rays_d, *nears, *fars, *w1, *b1, *w2, *b2;
+    float *out_image, *out_depth;
+    uint8_t *mask;
+    const float *g_image;
+    float *grad_image, *grad_ws, *partial;
+    const float *ent_grad_loss;
+    float ent_lambda;
+    float *grad_sigmas;
+    void *grad_rgbs;
+};
+
+// One lane's sample of a 16-sample window as loaded (`in`: inside the ray).
+template <typename rgb_t> struct RawWin {
+    float sg = 0.0f, dt = 0.0f, dl = 0.0f;
+    rgb_t c0 = (rgb_t)0.0f, c1 = (rgb_t)0.0f, c2 = (rgb_t)0.0f;
+    bool in = false;
+};
+
+template <typename rgb_t>
+__device__ __forceinline__ RawWin<rgb_t> load_win(const RayChainArgs &p, uint32_t offset,
+                                                  uint32_t num, uint32_t base, int lane) {
+    RawWin<rgb_t> v;
+    v.in = base < num && (uint32_t)lane < num - base;
+    if (v.in) {
+        const size_t i = (size_t)offset + base + lane;
+        const rgb_t *c = (const rgb_t *)p.rgbs + 3 * i;
+        v.sg = p.sigmas[i];
+        v.dt = p.deltas[2 * i];
+        v.dl = p.deltas[2 * i + 1];
+        v.c0 = c[0];
+        v.c1 = c[1];
+        v.c2 = c[2];
+    }
+    return v;
+}
+
+// The chain's operands of a loaded sample (lanes past the ray: no-ops).
+struct WinOps {
+    float a, om, cr, cg, cb;
+};
+template <typename rgb_t> __device__ __forceinline__ WinOps win_ops(const RawWin<rgb_t> &v) {
+    WinOps o;
+    o.a = v.in ? 1.0f - __expf(-v.sg * v.dt) : 0.0f;
+    o.om = 1.0f - o.a;
+    o.cr = to_f(v.c0);
+    o.cg = to_f(v.c1);
+    o.cb = to_f(v.c2);
+    return o;
+}
+
+#define DFHIP_16(STEP)                                                                      \
+    STEP(0) STEP(1) STEP(2) STEP(3) STEP(4) STEP(5) STEP(6) STEP(7) STEP(8) STEP(9) STEP(10) \
+    STEP(11) STEP(12) STEP(13) STEP(14) STEP(15)
+
+template <typename rgb_t>
+__global__ __launch_bounds__(kThreads) void k_ray_chain(RayChainArgs p) {
+    __shared__ W w;
+    __shared__ alignas(16) float s_x[kRays][kIn + 1];
+    __shared__ half_t s_dh[kRays][kHid];
+    __shared__ half_t s_h[kRays][kHid];
+    __shared__ float s_do[kRays][4];
+    const int q = threadIdx.x & (kSub - 1), r = threadIdx.x / kSub;
+    const int row_shift = (int)(threadIdx.x & 48);  // this row's bits in a wave ballot
+    const uint32_t N = p.N;
+    const uint32_t n = blockIdx.x * kRays + r;
+    const bool live = n < N;
+    const float T_thresh = p.T_thresh;
+    rgb_t *grad_rgbs = (rgb_t *)p.grad_rgbs;
+
+    // 1. the ray's record, its per-ray operands and its first window, issued
+    // ahead of the weight staging
+    uint32_t offset = 0, num = 0, num_all = 0;
+    float d[3] = {0.0f, 0.0f, 0.0f}, g[3] = {0.0f, 0.0f, 0.0f}, nr = 0.0f, fr = 0.0f;
+    if (live) {
+        offset = (uint32_t)p.rays[3 * n + 1];
+        num_all = (uint32_t)p.rays[3 * n + 2];
+        num = (offset + num_all <= p.M) ? num_all : 0u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = p.rays_d[3 * (size_t)n + c];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[k] = p.g_image[(size_t)k * N + n];
+        nr = p.nears[n];
+        fr = p.fars[n];
+    }
+    RawWin<rgb_t> cur = load_win<rgb_t>(p, offset, num, 0, q);
+
+    // 2. / 3. the head's f16 weights and this ray's frequency features
+    load_w(w, p.w1, p.b1, p.w2, p.b2);
+    if (live) features_part(d, q, s_x[r]);
+    else if (q == 0)
+        for (int i = 0; i < kIn; ++i) s_x[r][i] = 0.0f;
+    __syncthreads();
+
+    // 4. forward chain (k_composite_train_fwd_w)
+    rm::FwdChain c;
+    for (uint32_t base = 0; base < num && c.alive; base += 16) {
+        if (base != 0) cur = load_win<rgb_t>(p, offset, num, base, q);
+        const WinOps v = win_ops(cur);
+        const float dl = cur.dl;
+#define DFHIP_FSTEP(J) c.step<J>(v.a, v.om, v.cr, v.cg, v.cb, dl, T_thresh);
+        DFHIP_16(DFHIP_FSTEP)
+#undef DFHIP_FSTEP
+    }
+    const float wsv = c.ws, rf = c.r, gf = c.g, bf = c.b;
+    if (q == 0 && live) {
+        p.ws[n] = wsv;
+        p.depth[n] = c.d;
+        p.image[3 * (size_t)n + 0] = rf;
+        p.image[3 * (size_t)n + 1] = gf;
+        p.image[3 * (size_t)n + 2] = bf;
+    }
+
+    // 5. the head (k_head_bwd_net<true>) on the register values
+    float bg[3], dout[3], gw;
+    {
+        float x[kIn], h[kPer], o[kOut];
+        load_x(s_x[r], true, x);
+        mlp_part(w, x, q, h, o);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) bg[k] = sigmoid16(o[k]);
+        float sw = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sw = sw + g[k] * bg[k];
+        gw = -sw + entropy_grad(N, wsv, p.ent_grad_loss, p.ent_lambda);
+        if (live && q == 0) {
+            const float t = 1.0f - wsv;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float img = k == 0 ? rf : (k == 1 ? gf : bf);
+                p.out_image[(size_t)k * N + n] = img + t * bg[k];
+                p.grad_image[3 * (size_t)n + k] = g[k];
+            }
+            const float dd = c.d - nr;
+            p.out_depth[n] = (dd < 0.0f ? 0.0f : dd) / (fr - nr);
+            p.mask[n] = nr < fr ? 1 : 0;
+            p.grad_ws[n] = gw;
+        }
+        const float t = live ? 1.0f - wsv : 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float dbg = r16(g[k] * t);             // grad of the f16 bg
+            dout[k] = r16(dbg * (1.0f - bg[k]) * bg[k]);  // sigmoid_backward, f16
+        }
+        // 7. the LDS images of the weight-gradient partials (written here, so
+        // h and dout do not stay live across the backward chain)
+#pragma unroll
+        for (int jj = 0; jj < kPer; ++jj) {
+            const int j = kPer * q + jj;
+            float a = 0.0f;
+#pragma unroll
+            for (int k = 0; k < kOut; ++k) a = fmaf(dout[k], w.w2[k * kHid + j], a);
+            s_dh[r][j] = (half_t)(h[jj] > 0.0f ? r16(a) : 0.0f);
+            s_h[r][j] = (half_t)h[jj];
+        }
+        if (q == 0)
+#pragma unroll
+            for (int k = 0; k < kOut; ++k) s_do[r][k] = dout[k];
+    }
+
+    // 6. compositing backward (k_composite_train_bwd_w<DENSE>, zero_tail = 0)
+    const float gr = g[0], gg = g[1], gb = g[2];
+#define DFHIP_SAMPLE_GRAD(I, WL, TL, RL, GL, BL, DT, CR, CG, CB)                              \
+    {                                                                                         \
+        grad_rgbs[3 * (I) + 0] = rm::grad_cast<float, rgb_t>(gr * (WL));                      \
+        grad_rgbs[3 * (I) + 1] = rm::grad_cast<float, rgb_t>(gg * (WL));                      \
+        grad_rgbs[3 * (I) + 2] = rm::grad_cast<float, rgb_t>(gb * (WL));                      \
+        float acc = fmaf(gr, fmaf((TL), (CR), -(rf - (RL))), gg * fmaf((TL), (CG), -(gf - (GL)))); \
+        acc = fmaf(gb, fmaf((TL), (CB), -(bf - (BL))), acc);                                  \
+        acc = fmaf(gw, 1.0f - wsv, acc);                                                      \
+        p.grad_sigmas[(I)] = (DT) * acc;                                                      \
+    }
+    uint32_t done = 0;  // samples taken (the reference loop's final i)
+    rm::BwdChain b;
+    for (uint32_t base = 0; base < num && b.alive; base += 16) {
+        cur = load_win<rgb_t>(p, offset, num, base, q);
+        const WinOps v = win_ops(cur);
+        b.wl = b.Tl = b.rl = b.gl = b.bl = 0.0f;
+        b.taken = false;
+#define DFHIP_BSTEP(J) b.step<J>(q, v.a, v.om, v.cr, v.cg, v.cb, T_thresh);
+        DFHIP_16(DFHIP_BSTEP)
+#undef DFHIP_BSTEP
+        const bool taken = b.taken && cur.in;
+        if (taken) {
+            const size_t i = (size_t)offset + base + q;
+            DFHIP_SAMPLE_GRAD(i, b.wl, b.Tl, b.rl, b.gl, b.bl, cur.dt, v.cr, v.cg, v.cb)
+        }
+        done = base + (uint32_t)__popcll((__ballot(taken) >> row_shift) & 0xFFFFull);
+    }
+#undef DFHIP_SAMPLE_GRAD
+    if (live) {
+        // rows [offset + done, offset + num) of this ray, clipped to M
+        const uint64_t end = min((uint64_t)offset + num_all, (uint64_t)p.M);
+        for (uint64_t row = (uint64_t)offset + done + q; row < end; row += 16) {
+            p.grad_sigmas[row] = 0.0f;
+            grad_rgbs[3 * row] = (rgb_t)0.0f;
+            grad_rgbs[3 * row + 1] = (rgb_t)0.0f;
+            grad_rgbs[3 * row + 2] = (rgb_t)0.0f;
+        }
+    }
+    // 8. / 9.
+    __syncthreads();
+    write_partials(s_x, s_dh, s_h, s_do, p.partial);
+}
+#undef DFHIP_16
 
 // Fixed-order sum of the per-block partials: block = 64 outputs, its 16
 // waves take every 16th partial, then a fixed-order sum of the 16.
@@ -696,6 +937,47 @@ extern "C" int dfhip_ray_head_forward_backward_entropy_loss_check(
     return ray_head_backward(N, g_image, ws, rays_d, w1, b1, w2, b2, nullptr, grad_image,
                              grad_ws, nullptr, partial, gw1, gb1, gw2, gb2, grad_loss, lambda,
                              stream, loss, &io, found_inf, defer_sum != 0);
+}
+
+extern "C" int dfhip_ray_chain_train(
+    int rgb_dtype, const float *sigmas, const void *rgbs, const float *deltas,
+    const int32_t *rays, uint32_t M, uint32_t N, float T_thresh, float *ws, float *depth,
+    float *image, const float *rays_d, const float *nears, const float *fars, const float *w1,
+    const float *b1, const float *w2, const float *b2, float *out_image, float *out_depth,
+    uint8_t *mask, const float *g_image, float *grad_image, float *grad_ws, float *partial,
+    float *gw1, float *gb1, float *gw2, float *gb2, const float *grad_loss, float lambda,
+    float *loss, float *found_inf, int defer_sum, float *grad_sigmas, void *grad_rgbs,
+    dfhip_stream_t stream) {
+    const char *name = "ray_chain_train";
+    if (N == 0) {
+        set_error("%s: N must be > 0", name);
+        return DFHIP_EINVAL;
+    }
+    if (!sigmas || !rgbs || !deltas || !rays || !ws || !depth || !image || !rays_d || !nears ||
+        !fars || !w1 || !b1 || !w2 || !b2 || !out_image || !out_depth || !mask || !g_image ||
+        !grad_image || !grad_ws || !partial || !gw1 || !gb1 || !gw2 || !gb2 || !grad_loss ||
+        !loss || !grad_sigmas || !grad_rgbs) {
+        set_error("%s: null pointer (only found_inf may be null)", name);
+        return DFHIP_EINVAL;
+    }
+    const hd::RayChainArgs a{sigmas, rgbs, deltas, rays, M, N, T_thresh, ws, depth, image,
+                             rays_d, nears, fars, w1, b1, w2, b2, out_image, out_depth, mask,
+                             g_image, grad_image, grad_ws, partial, grad_loss, lambda,
+                             grad_sigmas, grad_rgbs};
+    hipStream_t s = as_stream(stream);
+    const uint32_t blocks = ceil_div(N, (uint32_t)hd::kRays);
+    if (rgb_dtype == DFHIP_F32) hd::k_ray_chain<float><<<blocks, hd::kThreads, 0, s>>>(a);
+    else if (rgb_dtype == DFHIP_F16) hd::k_ray_chain<half_t><<<blocks, hd::kThreads, 0, s>>>(a);
+    else if (rgb_dtype == DFHIP_BF16) hd::k_ray_chain<bf16_t><<<blocks, hd::kThreads, 0, s>>>(a);
+    else {
+        set_error("%s: rgb dtype must be f32, f16 or bf16 (got %d)", name, rgb_dtype);
+        return DFHIP_EDTYPE;
+    }
+    // defer_sum: the caller sums the partials later (dfhip_param_grad_sums)
+    if (!defer_sum)
+        hd::k_head_wsum<<<ceil_div((uint32_t)hd::kParams, 64u) + 1u, 1024, 0, s>>>(
+            partial, blocks, gw1, gb1, gw2, gb2, ws, N, lambda, loss, found_inf);
+    return check_launch(name);
 }
 
 extern "C" int dfhip_param_grad_sums(const float *mlp_partial, uint32_t mlp_parts, float *gw1,

@@ -30,7 +30,9 @@ head's weight-gradient sums and the entropy loss are one launch after the
 field backward (merged_grad_sums); the sums that write parameter gradients
 report a non-finite value themselves, so the optimizer launches no check
 (fold_overflow_check); the optimizer's finalize stores the live sample count
-into model.step_counter (store_live_count).
+into model.step_counter (store_live_count); compositing, the ray head and the
+compositing backward are one launch, dfhip_ray_chain_train (fused_ray_chain,
+tests/test_gpu_ray_chain.py).
 
 Every launch sits in a _dfhip.timed region with its algorithmic bytes (the
 regions are no-ops unless a kernel timer is installed, and the graph is
@@ -405,11 +407,6 @@ class NativeAlbedoStep:
                      ptr(self.m_dev), cap, ptr(self.sigma), ptr(self.color), ptr(self.normal),
                      ptr(self.orient_partial), self.lam_orient, ptr(self.orient), None, stream())
             rgb = self.color
-        # compositing (raymarching.py:238-269)
-        with T("composite_rays_train_forward", 32 * N, md, 4 + 3 * hb + 8):
-            _raymarching.composite_rays_train_forward_mixed(
-                self.sigma, rgb, self.deltas, self.rays, cap, N, 1e-4, self.ws, self.depth,
-                self.image)
         # ray head (renderer.py:536-551) and the entropy regulariser (utils.py:386-391)
         bw = self._bg_weights()
         # the injected SDS gradient does not depend on pred_rgb: with the
@@ -420,6 +417,27 @@ class NativeAlbedoStep:
         fi = self.found_inf  # the folded overflow check's flag, or None
         # the head's weight sum and the entropy loss wait for the field's sum
         defer = combined and self.merged_sums
+        # compositing, head and compositing backward as one launch (albedo,
+        # one pass): the per-ray chain never leaves its sixteen lanes
+        chain = defer and bool(getattr(self.trainer, "fused_ray_chain", True))
+        self.ray_chain = chain  # (tests: which form the captured step took)
+        if chain:
+            with T("ray_chain", (32 + 120 + 44) * N, md,
+                   (4 + 3 * hb + 8) + (4 + 3 * hb + 8 + 4 + 3 * hb)):
+                call("dfhip_ray_chain_train", _dfhip._DTYPE[rgb.dtype], ptr(self.sigma), ptr(rgb),
+                     ptr(self.deltas), ptr(self.rays), cap, N, 1e-4, ptr(self.ws),
+                     ptr(self.depth), ptr(self.image), ptr(self.rays_d), ptr(self.nears),
+                     ptr(self.fars), *[ptr(w) for w in bw], ptr(self.out_image),
+                     ptr(self.out_depth), ptr(self.mask), ptr(self.g_image),
+                     ptr(self.grad_image), ptr(self.grad_ws), ptr(self.head_partial),
+                     *[ptr(g) for g in self._bg_grads()], ptr(scale), self.lam, ptr(self.loss),
+                     ptr(fi), 1, ptr(self.grad_sigma), ptr(self.grad_albedo), stream())
+            return self._field_backward(fi, defer, hb)
+        # compositing (raymarching.py:238-269)
+        with T("composite_rays_train_forward", 32 * N, md, 4 + 3 * hb + 8):
+            _raymarching.composite_rays_train_forward_mixed(
+                self.sigma, rgb, self.deltas, self.rays, cap, N, 1e-4, self.ws, self.depth,
+                self.image)
         if not combined:
             with T("ray_head_forward", 60 * N):
                 call("dfhip_ray_head_forward", N, ptr(self.ws), ptr(self.depth), ptr(self.image),
@@ -480,7 +498,16 @@ class NativeAlbedoStep:
                      ptr(self.m_dev), cap, ptr(self.grad_sigma), ptr(self.grad_color),
                      ptr(scale), self.lam_orient, ptr(self.grad_sigma_field),
                      ptr(self.grad_albedo), stream())
+        return self._field_backward(fi, defer, hb)
+
+    def _field_backward(self, fi, defer, hb):
+        """The field MLP's backward and the parameter-gradient sums (fi: the
+        overflow flag or None; defer: the head's sums and the entropy loss
+        were left to the merged launch).  Returns the loss tensor."""
         from gridencoder.grid import _parts
+        m, N, T, mf = self.trainer.model, self.N, _dfhip.timed, self.m_field
+        S, Hb, gridtype, align, _ = self.meta
+        gbw = self._bg_grads()
         # features + density / albedo gradients + positions in, feature
         # gradients out (the weight gradients are per-workgroup partials)
         per_bwd = 2 * self.L * self.C * hb + 4 + 3 * hb + 12

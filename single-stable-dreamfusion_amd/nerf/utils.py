@@ -332,6 +332,10 @@ class Trainer(object):
         #  - the table copy and corner quads built by extra workgroups of the
         #    march's count launch
         self.quads_in_march = True
+        #  - compositing forward, ray head and compositing backward as one
+        #    launch (dfhip_ray_chain_train; albedo, one pass, with the merged
+        #    sums)
+        self.fused_ray_chain = True
         # graph-replayed steps through the reference-API modules (no native
         # step, model.fused_field False): the host-count march, then a graph
         # per sample-count bucket (nerf/graph.py BucketedModuleStep)
