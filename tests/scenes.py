@@ -59,3 +59,26 @@ def march_inputs(h=128, w=128, seed=0, radius=0.5, noise=0.002, min_near=0.2):
     noises = np.random.default_rng(seed + 100).random(rays_o.shape[0], dtype=np.float32)
     bf = sphere_bitfield(radius, noise, seed)
     return rays_o, rays_d, nears, fars, noises, bf
+
+
+def random_bitfield(C, H, seed):
+    """Occupancy bitfield of C cascades of H^3 cells, each bit set with
+    probability 1/8: every byte is the AND of three independent uniform uint8
+    draws (no cell table, so H = 512 stays cheap)."""
+    r = np.random.default_rng(seed)
+    n = C * H ** 3 // 8
+    a = r.integers(0, 256, n, dtype=np.uint8)
+    a &= r.integers(0, 256, n, dtype=np.uint8)
+    a &= r.integers(0, 256, n, dtype=np.uint8)
+    return a
+
+
+def march_inputs_general(h, w, seed, bound, radius, min_near):
+    """march_inputs for a box of +-bound and a camera at `radius` (no
+    bitfield): rays_o, rays_d, nears, fars, noises, with march_inputs'
+    noises."""
+    rays_o, rays_d = camera_rays(h, w, seed, radius=radius)
+    aabb = np.array([-bound] * 3 + [bound] * 3, np.float32)
+    nears, fars = oracle.near_far_from_aabb(rays_o, rays_d, aabb, min_near)
+    noises = np.random.default_rng(seed + 100).random(rays_o.shape[0], dtype=np.float32)
+    return rays_o, rays_d, nears, fars, noises

@@ -136,3 +136,53 @@ def test_grid_refresh_matches_oracle(gpu, dtype):
     total = min(16, local)
     assert total > 0
     assert int(m.mean_count) == int(counts[:total, 0].astype(np.int64).sum() / total)
+
+
+def test_grid_refresh_two_cascades(gpu, monkeypatch):
+    """The refresh at --bound 2 (two cascades): the EMA, the mean and the
+    bitfield over both cascades' cells (dfhip_density_grid_ema at the second
+    cascade's offset, dfhip_packbits_mean over 2 * 128^3 cells).  The sigma
+    itself is not restated here (cascade 1 queries the field out to |x| = 2)."""
+    import main
+    from nerf.network_grid import NeRFNetwork
+    torch.manual_seed(0)
+    m = NeRFNetwork(main.parse_opt(["--text", "occupancy", "-O", "--bound", "2"])).to(gpu)
+    assert m.cascade == 2 and m.grid_size == 128
+    assert m.native_grid_update and m.density_grid.is_cuda
+    g = torch.Generator(device=gpu).manual_seed(5)
+    with torch.no_grad():
+        m.encoder.embeddings.uniform_(-0.5, 0.5, generator=g)
+        old = torch.rand(m.density_grid.shape, generator=g, device=gpu) * 2
+        old[torch.rand(old.shape, generator=g, device=gpu) < 0.05] = -1.0
+        m.density_grid.copy_(old)
+    old_np = old.cpu().numpy().astype(F32)
+    assert old_np.shape == (2, 128 ** 3)
+    native = []
+    inner = m._update_extra_state_native
+    monkeypatch.setattr(m, "_update_extra_state_native",
+                        lambda decay: (native.append(decay), inner(decay))[1])
+    m.grid_generator = torch.Generator(device=gpu).manual_seed(77)
+    with torch.autocast("cuda", dtype=torch.float16):
+        m.update_extra_state()
+    torch.cuda.synchronize()
+    assert native == [0.95]  # the native path was taken
+    grid = m.density_grid.cpu().numpy()
+    bits = m.density_bitfield.cpu().numpy()
+    mean = float(m.mean_density)
+    valid = old_np >= 0
+    for cas in range(2):
+        v = valid[cas]
+        assert 0.04 < (~v).mean() < 0.06
+        assert np.array_equal(grid[cas][~v], old_np[cas][~v]), f"cascade {cas}: invalid cells changed"
+        assert np.all(grid[cas][v] >= old_np[cas][v] * F32(0.95)), f"cascade {cas}: EMA below decay"
+        # the queried sigma reached this cascade: it raised some cells
+        assert np.any(grid[cas][v] > old_np[cas][v] * F32(0.95)), cas
+    want_mean = grid[valid].astype(np.float64).mean()
+    assert abs(mean - want_mean) <= 1e-6 * abs(want_mean), (mean, want_mean)
+    thresh = min(mean, float(m.density_thresh))
+    want_bits = oracle.packbits(grid.reshape(-1), thresh)
+    assert want_bits.shape == (2 * 128 ** 3 // 8,)
+    assert np.array_equal(bits.reshape(-1), want_bits), \
+        f"{int((bits.reshape(-1) != want_bits).sum())} bitfield bytes differ"
+    per_cascade = np.unpackbits(want_bits).reshape(2, -1).mean(1)
+    assert np.all(per_cascade > 0.01) and np.all(per_cascade < 0.99), per_cascade

@@ -105,6 +105,8 @@ def _march_gpu(gpu, rays_o, rays_d, nears, fars, noises, bf, **kw):
     max_steps = kw.get("max_steps", 512)
     cap = kw.get("cap", n * max_steps)
     zero_tail = kw.get("zero_tail", 128)
+    bound, dt_gamma = kw.get("bound", 1.0), kw.get("dt_gamma", 0.0)
+    C, H = kw.get("C", 1), kw.get("H", 128)
     rays = torch.empty(n, 3, dtype=torch.int32, device=gpu)
     counter = torch.zeros(2, dtype=torch.int32, device=gpu)
     bs = torch.empty(_raymarching.march_rays_train_scratch_ints(n), dtype=torch.int32, device=gpu)
@@ -115,15 +117,15 @@ def _march_gpu(gpu, rays_o, rays_d, nears, fars, noises, bf, **kw):
         # count pass keeps the samples, emit pass copies them (native train step)
         stage = torch.full((_raymarching.march_rays_train_stage_floats(n, max_steps),), 5.0,
                            device=gpu)
-        _raymarching.march_rays_train_count_staged(o, d, b, 1.0, 0.0, max_steps, n, 1, 128, ne,
-                                                   fa, rays, counter, no, bs, stage)
+        _raymarching.march_rays_train_count_staged(o, d, b, bound, dt_gamma, max_steps, n, C,
+                                                   H, ne, fa, rays, counter, no, bs, stage)
         _raymarching.march_rays_train_emit_staged(d, max_steps, n, cap, xyzs, dirs, deltas, rays,
                                                   bs, zero_tail, stage)
         return xyzs, dirs, deltas, rays, counter
-    _raymarching.march_rays_train_count(o, d, b, 1.0, 0.0, max_steps, n, 1, 128, ne, fa, rays,
-                                        counter, no, bs)
-    _raymarching.march_rays_train_emit(o, d, b, 1.0, 0.0, max_steps, n, 1, 128, cap, ne, fa, xyzs,
-                                       dirs, deltas, rays, no, bs, zero_tail)
+    _raymarching.march_rays_train_count(o, d, b, bound, dt_gamma, max_steps, n, C, H, ne, fa,
+                                        rays, counter, no, bs)
+    _raymarching.march_rays_train_emit(o, d, b, bound, dt_gamma, max_steps, n, C, H, cap, ne, fa,
+                                       xyzs, dirs, deltas, rays, no, bs, zero_tail)
     return xyzs, dirs, deltas, rays, counter
 
 

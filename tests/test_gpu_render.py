@@ -11,21 +11,25 @@ import numpy as np
 import pytest
 import torch
 
-from scenes import camera_rays, sphere_bitfield
+from scenes import camera_rays, random_bitfield, sphere_bitfield
 
 pytestmark = pytest.mark.gpu
 
 
-def _model(gpu, seed=0, scale=0.5, occupancy="sphere"):
+def _model(gpu, seed=0, scale=0.5, occupancy="sphere", extra=()):
     import main
     from nerf.network_grid import NeRFNetwork
     torch.manual_seed(seed)
-    opt = main.parse_opt(["--text", "render", "-O"])
+    opt = main.parse_opt(["--text", "render", "-O", *extra])
     m = NeRFNetwork(opt).to(gpu)
     with torch.no_grad():
         m.encoder.embeddings.uniform_(-scale, scale)
     if occupancy == "sphere":
         m.density_bitfield.copy_(torch.from_numpy(sphere_bitfield(0.6, 0.003, seed)).to(gpu))
+    elif occupancy == "random":  # every cascade, one cell in eight
+        bits = random_bitfield(m.cascade, m.grid_size, seed)
+        assert bits.shape == tuple(m.density_bitfield.shape)
+        m.density_bitfield.copy_(torch.from_numpy(bits).to(gpu))
     else:
         with torch.autocast("cuda", dtype=torch.float16):
             m.update_extra_state()
@@ -38,17 +42,18 @@ def _rays(gpu, h, w, seed, radius=1.6):
     return torch.from_numpy(o).to(gpu), torch.from_numpy(d).to(gpu)
 
 
-def _both(m, rays_o, rays_d, n_step_max, perturb=False, T_thresh=1e-4, max_steps=512):
+def _both(m, rays_o, rays_d, n_step_max, perturb=False, T_thresh=1e-4, max_steps=512,
+          dt_gamma=0.0):
     import raymarching
     nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, m.aabb_infer)
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
         field = m.native_infer_field("albedo", rays_o)
         assert field is not None
         torch.manual_seed(7)
-        fused = m._infer_fused(rays_o, rays_d, nears, fars, field, perturb, 0.0, max_steps,
+        fused = m._infer_fused(rays_o, rays_d, nears, fars, field, perturb, dt_gamma, max_steps,
                                T_thresh)
         torch.manual_seed(7)
-        loop = m._infer_loop(rays_o, rays_d, nears, fars, None, 1.0, "albedo", perturb, 0.0,
+        loop = m._infer_loop(rays_o, rays_d, nears, fars, None, 1.0, "albedo", perturb, dt_gamma,
                              max_steps, T_thresh, n_step_max=n_step_max)
     torch.cuda.synchronize()
     return [t.cpu().numpy() for t in fused], [t.cpu().numpy() for t in loop]
@@ -75,6 +80,31 @@ def test_fused_infer_perturbed_bit_exact(gpu):
     np.testing.assert_array_equal(fw, lw)
     np.testing.assert_array_equal(fi, li)
     np.testing.assert_array_equal(fd, ld)
+
+
+def _two_cascade_case(gpu, dt_gamma, perturb):
+    """bound 2 (two cascades), one cell in eight occupied in both, a camera
+    outside the level-0 box: the fused renderer's marcher takes the level from
+    the position and from dt."""
+    m = _model(gpu, 9, 1.0, "random", extra=("--bound", "2"))
+    assert m.cascade == 2 and m.bound == 2
+    rays_o, rays_d = _rays(gpu, 32, 32, 9, radius=2.6)
+    (fw, fd, fi), (lw, ld, li) = _both(m, rays_o, rays_d, n_step_max=1, perturb=perturb,
+                                       dt_gamma=dt_gamma)
+    assert (lw > 0).sum() > 100
+    np.testing.assert_array_equal(fw, lw)
+    np.testing.assert_array_equal(fd, ld)
+    np.testing.assert_array_equal(fi, li)
+
+
+@pytest.mark.parametrize("dt_gamma", [0.0, 1 / 128])
+def test_fused_infer_bit_exact_vs_nstep1_loop_two_cascades(gpu, dt_gamma):
+    _two_cascade_case(gpu, dt_gamma, perturb=False)
+
+
+@pytest.mark.parametrize("dt_gamma", [0.0, 1 / 128])
+def test_fused_infer_perturbed_bit_exact_two_cascades(gpu, dt_gamma):
+    _two_cascade_case(gpu, dt_gamma, perturb=True)
 
 
 def test_fused_infer_vs_default_schedule(gpu):
@@ -392,6 +422,69 @@ def test_ray_order_occupancy_cost_vs_numpy(gpu):
     c = want[o]
     span = c.max() - c.min()
     b = np.minimum(((c - c.min()) * (64 / span)).astype(np.int64), 63) if span > 0 else 0 * c
+    assert np.all(np.diff(b) >= 0)  # bucket order
+    for k in np.unique(b):  # stable inside a bucket
+        assert np.all(np.diff(o[b == k]) > 0)
+
+
+def test_ray_order_occupancy_cost_two_cascades(gpu):
+    """k_chunk_cost_occ at C = 2, bound = 2: the numpy restatement with the
+    level of each probe, max(level from position, level from dt_min) clamped
+    to [0, C - 1], hence mip_bound = min(2^level, bound), its f32 reciprocal
+    and the bitfield index fmaf(level, H^3, code).  Random bitfield (one cell
+    in eight, both cascades), ray origins around (0, 0, 4)."""
+    import _fieldmlp
+    import oracle
+    from scenes import random_bitfield
+    C, H, bound, cl, max_steps = 2, 128, 2.0, 6, 1024
+    rng = np.random.default_rng(6)
+    bitfield = random_bitfield(C, H, 6)
+    N = 64 * 24
+    ro = (rng.normal(size=(N, 3)) * 0.1 + np.array([0.0, 0.0, 4.0])).astype(np.float32)
+    tgt = (rng.random((N, 3)) * 3.2 - 1.6).astype(np.float32)
+    rd = tgt - ro
+    rd = (rd / np.linalg.norm(rd, axis=1, keepdims=True)).astype(np.float32)
+    aabb = np.array([-bound] * 3 + [bound] * 3, np.float32)
+    nears, fars = oracle.near_far_from_aabb(ro, rd, aabb, 0.05)
+    fars[::97] = nears[::97]  # rays missing the box: no probes
+    cost = torch.empty(N >> cl, dtype=torch.float32, device=gpu)
+    order = _fieldmlp.render_ray_order(
+        torch.from_numpy(ro).to(gpu), torch.from_numpy(rd).to(gpu), cl, cost=cost,
+        occ=(torch.from_numpy(nears).to(gpu), torch.from_numpy(fars).to(gpu),
+             torch.from_numpy(bitfield).to(gpu), bound, C, H, max_steps))
+    torch.cuda.synchronize()
+    # numpy restatement of k_chunk_cost_occ (render.hip), all rays at once
+    live = fars > nears
+    step = (fars - nears) / _f32(16)
+    dt_min = _f32(2.0) * _f32(1.7320508075688772) / _f32(max_steps)
+    ld = np.clip(np.frexp(_f32(np.float64(dt_min * _f32(H)) * 0.5))[1], 0, C - 1)
+    want = np.zeros(N >> cl, np.float64)
+    levels = []
+    for i in range(16):
+        t = _fma32(np.full(N, i + 0.5, np.float32), step, nears)
+        p = np.clip(_fma32(t[:, None], rd, ro), _f32(-bound), _f32(bound))
+        lp = np.clip(np.frexp(np.abs(p).max(1))[1], 0, C - 1)
+        level = np.maximum(lp, ld)
+        mip_bound = np.minimum(np.exp2(level).astype(np.float32), _f32(bound))
+        rbound = _f32(1.0) / mip_bound
+        assert rbound.dtype == np.float32
+        u = _fma32(p, rbound[:, None], np.ones_like(p)) * _f32(H / 2)
+        cell = np.clip(u, _f32(0), _f32(H - 1)).astype(np.int32)
+        code = oracle.morton3D(cell).astype(np.float32)
+        idx = _fma32(level.astype(np.float32), np.full(N, H ** 3, np.float32), code)
+        idx = idx.astype(np.int64)
+        bit = (bitfield[idx >> 3] >> (idx & 7).astype(np.uint8)) & 1
+        np.subtract.at(want, np.arange(N)[live] >> cl, bit[live].astype(np.float64))
+        levels.append(level[live])
+    share = np.bincount(np.concatenate(levels), minlength=C) / sum(len(a) for a in levels)
+    assert share.min() > 0.2, share  # both cascades are probed
+    assert len(np.unique(want)) > 4
+    np.testing.assert_array_equal(cost.cpu().numpy(), want.astype(np.float32))
+    o = order.cpu().numpy()
+    assert sorted(o.tolist()) == list(range(N >> cl))
+    c = want[o]
+    span = c.max() - c.min()
+    b = np.minimum(((c - c.min()) * (64 / span)).astype(np.int64), 63)
     assert np.all(np.diff(b) >= 0)  # bucket order
     for k in np.unique(b):  # stable inside a bucket
         assert np.all(np.diff(o[b == k]) > 0)
