@@ -116,6 +116,56 @@ __device__ void load_weights(WeightsG<E> &W, typename Id<WeightsTG<E>>::type *T,
         W.b3[i] = (i & 3) == 0 ? (float)(E)b3[i >> 2] : 0.0f;
 }
 
+// load_weights for a workgroup of exactly 256 threads: the same LDS contents,
+// with every global load issued before the first conversion (28 coalesced
+// dword loads per thread, one memory round trip).  load_weights' loops run to
+// a runtime bound, so they compile to a load, a full wait and a write per
+// step: some twenty dependent round trips before a kernel's first tile.
+template <bool PERM, typename E>
+__device__ __forceinline__ void load_weights_256(WeightsG<E> &W,
+                                                 typename Id<WeightsTG<E>>::type *T,
+                                                 const float *w1, const float *b1,
+                                                 const float *w2, const float *b2,
+                                                 const float *w3, const float *b3) {
+    const int t = threadIdx.x;
+    float x1[8], x2[16];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x1[j] = w1[t + 256 * j];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) x2[j] = w2[t + 256 * j];
+    const float x3 = w3[t];  // output t >> 6, neuron t & 63
+    const float y1 = b1[t & 63], y2 = b2[t & 63], y3 = b3[(t >> 2) & 3];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int i = t + 256 * j, n = i / kIn, f = i % kIn;
+        // perm_feature is its own inverse (it swaps the two 2-bit fields)
+        W.w1[n * kLd32 + (PERM ? perm_feature(f) : f)] = (E)x1[j];
+        if (T) T->w1t[f * kLd64 + n] = (E)x1[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int i = t + 256 * j;
+        const E v = (E)x2[j];
+        W.w2[(i / kHid) * kLd64 + i % kHid] = v;
+        if (T) T->w2t[(i % kHid) * kLd64 + i / kHid] = v;
+    }
+    {
+        const int r = t >> 6, n2 = t & 63;
+        W.w3[(4 * r) * kLd64 + n2] = (E)x3;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) W.w3[(4 * r + k) * kLd64 + n2] = (E)0.0f;
+        if (T)
+            *reinterpret_cast<typename Elem<E>::v8 *>(T->w3t + n2 * kLd32 + 8 * r) =
+                typename Elem<E>::v8{(E)x3,   (E)0.0f, (E)0.0f, (E)0.0f,
+                                     (E)0.0f, (E)0.0f, (E)0.0f, (E)0.0f};
+    }
+    if (t < kHid) {
+        W.b1[t] = (float)(E)y1;
+        W.b2[t] = (float)(E)y2;
+    }
+    if (t < 16) W.b3[t] = (t & 3) == 0 ? (float)(E)y3 : 0.0f;
+}
+
 // A operand, natural k order: row `row` of a row-major [*, ld] f16 matrix,
 // k = 8h .. 8h+7 (+ koff).
 template <typename E>

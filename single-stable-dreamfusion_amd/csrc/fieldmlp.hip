@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256, 5) void k_field_fwd_fused(
     __shared__ WeightsG<E> W;
     __shared__ LevelK LK[kLevels];
     const bool align = align_corners != 0;
-    load_weights<true>(W, nullptr, w1, b1, w2, b2, w3, b3);
+    load_weights_256<true>(W, nullptr, w1, b1, w2, b2, w3, b3);  // (256 threads)
     stage_levels(LK, offsets, lv, gridtype, align);
     __syncthreads();
     const uint32_t M = active_count(m_dev, cap);
@@ -191,6 +191,13 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(const E *__restrict__ x, const 
 // 2 waves per SIMD instead of 1, no per-element LDS writes, no bias VALU sums.
 // Each partial entry is written by exactly one lane of the workgroup; the
 // fixed-order k_field_wgrad_sum over workgroups keeps the result deterministic.
+// Nothing in the round loop waits for memory it has just asked for: the next
+// round's inputs are loaded without a bounds branch (load_tile) while this
+// round runs, and the weights are staged in one round trip (load_weights_256).
+// A round is then bound by instruction issue (about 540 instructions per wave,
+// two waves per SIMD in the same phase); one barrier per round instead of two,
+// with the weight-gradient products of round r - 1 inside round r, was
+// measured and changed nothing.
 constexpr int kBwdWaves = 4;
 // Weight operands held in registers for the whole kernel instead of re-read
 // from LDS every tile (bit 0: W2 of the forward and W2^T, 64 VGPRs; bit 1:
@@ -203,9 +210,6 @@ constexpr int kBwdWaves = 4;
 #define DFHIP_BWD_WREG 31
 #endif
 constexpr int kBwdWreg = DFHIP_BWD_WREG;
-#ifndef DFHIP_BWD_PINGPONG
-#define DFHIP_BWD_PINGPONG 0
-#endif
 constexpr int kStLd = 312;  // stage row stride (halves): 156 dwords = 4 mod 64 -> the
                             // 32 lanes of an 8-byte write hit 64 distinct banks
 constexpr int kColX = 0, kColA1 = 32, kColA2 = 96, kColD1 = 160, kColD2 = 224, kColDO = 288;
@@ -258,7 +262,12 @@ __device__ __forceinline__ void st_write4(StageT<E> &S, int sample, int col, E v
 // One wave's inputs for a 16-sample tile: encoder features (every lane), and
 // the incoming gradient of the lane group's output (h = 0: the density's, with
 // the position for the Gaussian blob; h > 0: albedo channel h - 1's) — as
-// loaded (no conversion), so a prefetch does not wait for its loads.
+// loaded: no conversion and no select, so a prefetch does not wait for its
+// loads.  Every lane loads, from the row of its sample clamped to the last
+// live row (in bounds: the buffers hold cap >= 1 rows); the chain zeroes what
+// a sample past the live count contributes.  (Loads under `sample < M`
+// compiled to branches with a full memory wait at their join, paid at the
+// start of every round.)
 template <typename E, typename rgb_t>
 struct TileIn {
     typename Elem<E>::v8 xb;
@@ -272,19 +281,20 @@ template <typename E, typename rgb_t, bool MLP_ONLY = false>
 __device__ __forceinline__ void load_tile(TileIn<E, rgb_t> &g, uint32_t tile, const E *enc,
                                           const float *xyz, const float *grad_sigma,
                                           const rgb_t *grad_rgb, uint32_t M, int c, int h) {
+    const uint32_t last = M ? M - 1u : 0u;
     const uint32_t sample = tile * 16 + c;
-    g.xb = load_x(enc, sample, M, h);
+    const size_t row = sample < last ? sample : last;
+    g.xb = *reinterpret_cast<const typename Elem<E>::v8 *>(enc + row * kIn + 8 * h);
     if constexpr (MLP_ONLY) {
         g.gs = 0.0f;
         g.xyz[0] = g.xyz[1] = g.xyz[2] = 0.0f;
-        g.grgb = sample < M ? grad_rgb[(size_t)sample * kOut + h] : (rgb_t)0.0f;
+        g.grgb = grad_rgb[row * kOut + h];
         return;
     }
-    const bool v = (h == 0) && sample < M;
 #pragma unroll
-    for (int d = 0; d < 3; ++d) g.xyz[d] = v ? xyz[(size_t)sample * 3 + d] : 0.0f;
-    g.gs = v ? grad_sigma[sample] : 0.0f;
-    g.grgb = (h > 0 && sample < M) ? grad_rgb[(size_t)sample * 3 + h - 1] : (rgb_t)0.0f;
+    for (int d = 0; d < 3; ++d) g.xyz[d] = xyz[row * 3 + d];
+    g.gs = grad_sigma[row];
+    g.grgb = grad_rgb[row * 3 + (h > 0 ? h - 1 : 0)];
 }
 
 // PERM: enc holds the fused forward's permuted feature order (k_field_fwd_fused);
@@ -305,7 +315,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
     __shared__ WeightsG<E> W;
     __shared__ WeightsTG<E> T;
     __shared__ StageT<E> stage[kBwdWaves];
-    load_weights<PERM>(W, &T, w1, b1, w2, b2, w3, b3);
+    load_weights_256<PERM>(W, &T, w1, b1, w2, b2, w3, b3);  // (256 threads)
     const uint32_t M = active_count(m_dev, cap);
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63, c = lane & 15, h = lane >> 4;
@@ -344,9 +354,10 @@ __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
     auto round_of = [&](const TileIn<E, rgb_t> &cur, uint32_t tile) {
         const uint32_t sample = tile * 16 + c;
         const bool valid = sample < M;
+        const v8 xb = valid ? cur.xb : v8{};  // (the prefetch loads a clamped row)
         FwdG<E, true> F;  // packed activations (f16 pairs per VGPR)
         forward_tile<E, true, (kBwdWreg & 1) != 0, (kBwdWreg & 8) != 0, (kBwdWreg & 16) != 0>(
-            W, cur.xb, c, h, F, w2op, w1op, w3op);
+            W, xb, c, h, F, w2op, w1op, w3op);
         // dL/d(output h), in E as autocast's backward produces it: lane group h
         // holds output h (F.o[0]) and its incoming gradient
         E dOh = (E)0.0f;
@@ -433,7 +444,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
         }
         // [sample][neuron] image of the tile (invalid samples: dO = 0 so every
         // gradient row is zero and they add nothing below)
-        *reinterpret_cast<v8 *>(S.v + c * kStLd + kColX + 8 * h) = cur.xb;
+        *reinterpret_cast<v8 *>(S.v + c * kStLd + kColX + 8 * h) = xb;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int col = 16 * t + 4 * h;
@@ -490,23 +501,8 @@ __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
         }
         __syncthreads();  // the images are rewritten next round
     };
-    // two input buffers in turn: round r + 1's loads are issued before round
-    // r runs and first waited on in round r + 1 (a copy of the prefetched
-    // registers at the end of each round would wait for them there)
+    // round r + 1's inputs are loaded while round r runs
     uint32_t tile = blockIdx.x * kBwdWaves + wave;
-#if DFHIP_BWD_PINGPONG
-    TileIn<E, rgb_t> ta, tb;
-    load_tile<E, rgb_t>(ta, tile, enc, xyz, grad_sigma, grad_rgb, M, c, h);
-    for (uint32_t round = 0; round < rounds; round += 2) {
-        load_tile<E, rgb_t>(tb, tile + per_round, enc, xyz, grad_sigma, grad_rgb, M, c, h);
-        round_of(ta, tile);
-        tile += per_round;
-        if (round + 1 >= rounds) break;  // uniform
-        load_tile<E, rgb_t>(ta, tile + per_round, enc, xyz, grad_sigma, grad_rgb, M, c, h);
-        round_of(tb, tile);
-        tile += per_round;
-    }
-#else
     TileIn<E, rgb_t> cur;
     load_tile<E, rgb_t, MLP_ONLY>(cur, tile, enc, xyz, grad_sigma, grad_rgb, M, c, h);
     for (uint32_t round = 0; round < rounds; ++round, tile += per_round) {
@@ -516,7 +512,6 @@ __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
         round_of(cur, tile);
         cur = nxt;
     }
-#endif
     if constexpr (MLP_ONLY) {
         // feature-gradient rows past the live count: zeros (64 bytes per row)
         for (size_t i = (size_t)M * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
