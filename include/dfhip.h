@@ -472,6 +472,68 @@ int dfhip_resmlp_field_backward(const float *xyz, const float *const *params,
                                 int grad_albedo_dtype, uint32_t M, float *dx, void *scratch,
                                 float *const *grads, int accumulate, dfhip_stream_t stream);
 
+/* ---------------------------------------------------------------- fused voxel field
+ * The DVGO backbone of nerf/network_dvgo.py (reference nerf/network.py:245-268
+ * with weight = None) under fp16 autocast: frozen dense volumes, a trainable
+ * colour MLP.  xyz: [M, 3] f32 in [-bound, bound].  Coordinate map (f32, in
+ * this order): s = (x + bound) * (1 / (2 bound)), y and z swapped,
+ * (s - 0.5) * 1.25 + 0.5, p = s * (box_max - box_min) + box_min; a row is
+ * inside when box_min <= p <= box_max on all axes (inclusive).  Trilinear
+ * sample at g = (((p - box_min) / (box_max - box_min)) * 2 - 1 + 1) * 0.5 *
+ * (N - 1) per axis: cell floor(g), weights (floor(g) + 1 - g) and
+ * (g - floor(g)) not clamped, corner indices clamped to [0, N - 1], the eight
+ * products summed in the order of the reference's grid_sample_3d
+ * (osr_fine.py:559-673).  density: [Nx, Ny, Nz] f32 (the checkpoint's layout,
+ * z fastest); k0: [Nx, Ny, Nz, C] f32 (channel last, 1 <= C).  box: HOST array
+ * of six floats, box_min xyz then box_max xyz.
+ *   sigma  = 10 * softplus(raw + act_shift) (f32), raw = 0 outside the box;
+ *   albedo = sigmoid(rgbnet(cat(k0 sample, PE(u), view))) (f16) inside the
+ *            box, 0.5 outside, with u = (p - box_min) / (box_max - box_min),
+ *            PE(u) = [u, sin(u_d 2^i), cos(u_d 2^i)] (d major, i = 0 ..
+ *            pos_freqs - 1; absent when pos_freqs = 0) and view: view_dim f32
+ *            constants (the encoding of the fixed view direction, device
+ *            pointer, may be NULL when view_dim = 0).
+ * dim0 = C + (pos_freqs ? 3 + 6 pos_freqs : 0) + view_dim <= 96.  The feature
+ * row is rounded to f16 at the first Linear; Linears are f16 GEMMs with f32
+ * accumulation and f16 outputs, ReLU between them, sigmoid in f32 of the f16
+ * output, rounded to f16.
+ * params: host array of 6 device pointers to the f32 tensors in
+ * rgbnet.state_dict() order (BasicMLP, width 128, depth 3): net.0.weight
+ * [128, dim0], net.0.bias [128], net.2.0.weight [128, 128], net.2.0.bias
+ * [128], net.3.weight [3, 128], net.3.bias [3].
+ * albedo NULL: the density branch only (params may then be NULL). */
+int dfhip_voxel_field_forward(const float *xyz, const float *density, const float *k0,
+                              uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
+                              uint32_t pos_freqs, const float *view, uint32_t view_dim,
+                              const float *box, float bound, float act_shift,
+                              const float *const *params, float *sigma, void *albedo,
+                              uint32_t M, dfhip_stream_t stream);
+/* Backward: the f32 gradients of the six rgbnet tensors for grad_albedo
+ * [M, 3] (grad_albedo_dtype F16 / F32; rounded to f16 as the gradient of an
+ * f16 albedo arrives).  The volumes are frozen and the positions are leaves:
+ * no other gradient exists, and a gradient of sigma has nowhere to go.  The
+ * forward is recomputed; rows outside the box contribute nothing.  grads: host
+ * array of 6 device pointers shaped as params (overwritten, or added into with
+ * accumulate).  scratch: dfhip_voxel_field_backward_scratch(M, dim0) bytes,
+ * 16-byte aligned.  Deterministic: per-split partials summed in a fixed order,
+ * no float atomics. */
+uint64_t dfhip_voxel_field_backward_scratch(uint32_t M, uint32_t dim0);
+int dfhip_voxel_field_backward(const float *xyz, const float *k0, uint32_t Nx, uint32_t Ny,
+                               uint32_t Nz, uint32_t C, uint32_t pos_freqs, const float *view,
+                               uint32_t view_dim, const float *box, float bound,
+                               const float *const *params, const void *grad_albedo,
+                               int grad_albedo_dtype, uint32_t M, void *scratch,
+                               float *const *grads, int accumulate, dfhip_stream_t stream);
+/* normal [M, 3] f32 = -d sigma / d x in closed form: the derivative of the
+ * trilinear weights in the cell of the same floor with the same clamped
+ * corners (0 across a clamped edge), times 10 * sigmoid(raw + act_shift),
+ * times the chain factors of the coordinate map (autograd's order: * (N - 1),
+ * * 0.5, * 2, / extent, * extent, * 1.25, * 1 / (2 bound)), the y / z swap
+ * undone.  Rows outside the box get 0.  Not normalised. */
+int dfhip_voxel_normal(const float *xyz, const float *density, uint32_t Nx, uint32_t Ny,
+                       uint32_t Nz, const float *box, float bound, float act_shift,
+                       float *normal, uint32_t M, dfhip_stream_t stream);
+
 /* Fused grid field (native path of nerf/field.py): tiled-grid encoding
  * (gridencoder.cu:75-178 arithmetic, f16 table) + the MLP/heads above in ONE
  * kernel.  xyz: [cap, 3] f32 in [-bound, bound] (mapped to [0,1] as

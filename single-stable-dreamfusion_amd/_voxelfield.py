@@ -1,0 +1,127 @@
+"""Native fused voxel field (csrc/voxelfield.hip): the DVGO backbone's
+coordinate map, trilinear density / feature samples, position and view
+encodings, colour MLP dim0 -> 128 -> 128 -> 3 and activations (reference
+nerf/network.py:245-268 under fp16 autocast), its parameter-gradient backward
+and the closed-form normal.  No reference pybind counterpart: the reference
+runs this as torch ops."""
+import ctypes
+
+import torch
+
+import _dfhip as _d
+from _dfhip import call, checked, ptr, stream
+
+HIDDEN, OUT, MAX_IN = 128, 3, 96
+# rows of one MFMA tile (a wave's samples per pass) and rows a workgroup of
+# the forward kernel takes per pass (8 waves)
+ROW_TILE, WORKGROUP_ROWS = 16, 128
+
+
+def shapes(dim0):
+    """rgbnet.state_dict() order (include/dfhip.h)."""
+    return [(HIDDEN, dim0), (HIDDEN,), (HIDDEN, HIDDEN), (HIDDEN,), (OUT, HIDDEN), (OUT,)]
+
+
+class Volume:
+    """The frozen operands of one checkpoint on one device: density
+    [Nx, Ny, Nz] f32, k0 [Nx, Ny, Nz, C] f32 (channel last), the box (host
+    floats: min xyz, max xyz), the number of position frequencies and the f32
+    view encoding [view_dim] (or None)."""
+
+    def __init__(self, density, k0, box, pos_freqs, view):
+        checked(density, "density")
+        checked(k0, "k0")
+        if density.dtype != torch.float32 or k0.dtype != torch.float32:
+            raise RuntimeError("density and k0 must be float32 tensors")
+        if density.dim() != 3 or k0.dim() != 4 or tuple(k0.shape[:3]) != tuple(density.shape):
+            raise RuntimeError("density [Nx, Ny, Nz] and k0 [Nx, Ny, Nz, C] expected")
+        if view is not None:
+            checked(view, "view")
+            if view.dtype != torch.float32 or view.dim() != 1:
+                raise RuntimeError("view must be a float32 vector")
+        if len(box) != 6:
+            raise RuntimeError("box must hold six floats: min xyz, max xyz")
+        self.density, self.k0, self.view = density, k0, view
+        self.box = (ctypes.c_float * 6)(*[float(v) for v in box])
+        self.n = tuple(int(v) for v in density.shape)
+        self.C, self.pos_freqs = int(k0.shape[3]), int(pos_freqs)
+        self.view_dim = 0 if view is None else int(view.numel())
+        self.dim0 = self.C + (3 + 6 * self.pos_freqs if self.pos_freqs else 0) + self.view_dim
+
+
+def backward_scratch_bytes(M, dim0):
+    return int(_d.load().dfhip_voxel_field_backward_scratch(int(M), int(dim0)))
+
+
+def _f32(t, what):
+    checked(t, what)
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{what} must be a float32 tensor")
+
+
+def _pointers(ts, dim0, what):
+    want = shapes(dim0)
+    if len(ts) != len(want):
+        raise RuntimeError(f"expected the {len(want)} rgbnet tensors in state_dict order")
+    for i, (t, shp) in enumerate(zip(ts, want)):
+        _f32(t, f"{what}{i}")
+        if tuple(t.shape) != shp:
+            raise RuntimeError(f"{what}{i} must have shape {shp}, got {tuple(t.shape)}")
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _positions(xyz):
+    _f32(xyz, "xyz")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError("xyz [M, 3] f32 expected")
+    return xyz.shape[0]
+
+
+def field_forward(xyz, vol, bound, act_shift, params, sigma, albedo=None):
+    """xyz [M, 3] f32 -> sigma [M] f32, albedo [M, 3] f16 (None: density only,
+    params may then be None)."""
+    M = _positions(xyz)
+    _f32(sigma, "sigma")
+    if tuple(sigma.shape) != (M,):
+        raise RuntimeError("sigma [M] f32 expected")
+    pp = None
+    if albedo is not None:
+        checked(albedo, "albedo")
+        if tuple(albedo.shape) != (M, 3) or albedo.dtype != torch.float16:
+            raise RuntimeError("albedo [M, 3] f16 expected")
+        pp = _pointers(params, vol.dim0, "param")
+    call("dfhip_voxel_field_forward", ptr(xyz), ptr(vol.density), ptr(vol.k0), *vol.n, vol.C,
+         vol.pos_freqs, ptr(vol.view), vol.view_dim, vol.box, float(bound), float(act_shift), pp,
+         ptr(sigma), ptr(albedo), M, stream())
+
+
+def field_backward(xyz, vol, bound, params, grad_albedo, grads, accumulate=False, scratch=None):
+    """grads: the 6 f32 gradients shaped as params (overwritten, or added into
+    with accumulate).  scratch: uint8 tensor of backward_scratch_bytes(M,
+    dim0) or None (allocated)."""
+    M = _positions(xyz)
+    checked(grad_albedo, "grad_albedo")
+    if grad_albedo.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("grad_albedo must be float16 or float32")
+    if tuple(grad_albedo.shape) != (M, 3):
+        raise RuntimeError("grad_albedo [M, 3] expected")
+    need = backward_scratch_bytes(M, vol.dim0)
+    if scratch is None:
+        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=xyz.device)
+    checked(scratch, "scratch", "u8")
+    if scratch.numel() < need:
+        raise RuntimeError(f"scratch must hold {need} bytes")
+    call("dfhip_voxel_field_backward", ptr(xyz), ptr(vol.k0), *vol.n, vol.C, vol.pos_freqs,
+         ptr(vol.view), vol.view_dim, vol.box, float(bound), _pointers(params, vol.dim0, "param"),
+         ptr(grad_albedo), _d.dtype_code(grad_albedo, "grad_albedo"), M, ptr(scratch),
+         _pointers(grads, vol.dim0, "grad"), int(bool(accumulate)), stream())
+
+
+def normal(xyz, vol, bound, act_shift, out):
+    """xyz [M, 3] f32 -> out [M, 3] f32 = -d sigma / d x (not normalised)."""
+    M = _positions(xyz)
+    _f32(out, "normal")
+    if tuple(out.shape) != (M, 3):
+        raise RuntimeError("normal [M, 3] f32 expected")
+    call("dfhip_voxel_normal", ptr(xyz), ptr(vol.density), *vol.n, vol.box, float(bound),
+         float(act_shift), ptr(out), M, stream())

@@ -1,0 +1,543 @@
+// Fused voxel field on MFMA (gfx950): the DVGO backbone of
+// nerf/network_dvgo.py.  Frozen dense volumes (density [Nx, Ny, Nz], k0
+// [Nx, Ny, Nz, C] channel last, both f32), a trainable colour MLP
+// dim0 -> 128 -> 128 -> 3 (BasicMLP, ReLU).
+//
+// Behavioural spec: nerf/network.py:245-268 (to_our_coor, common_forward with
+// weight = None), frameworks/nerf/modules/osr_fine.py:559-673 (the trilinear
+// sample), dvgo_fine.py:45-54 (query_rgb), modules/utils.py:129-131
+// (position_encoding), decoders/mlps.py:59-73 (BasicMLP), run under
+// torch.autocast(fp16): map, sample, activation and encodings are f32, the
+// feature row is cast to f16 at the first Linear, every Linear is an f16
+// GEMM with f32 accumulation and an f16 output, ReLU and sigmoid act on f16.
+//
+// Forward: one launch.  A workgroup of 8 waves keeps the f16 weights in LDS
+// (65 KiB); a wave takes 16 samples through map, gathers, encodings and the
+// three layers in registers (voxel_common.h).  The four lane groups of a
+// sample fill its 96-feature row, every fourth feature each, into a per-wave
+// LDS image (26 KiB per workgroup) and read their operands back from it.  A
+// tile with no row inside the box skips the MLP.
+//
+// Backward (parameter gradients only: the volumes are frozen and the
+// positions are leaves), three launches per chunk of up to 65536 samples:
+//   1. the forward again with the transposed second layer also in LDS
+//      (101 KiB), then the output gradients of the three Linears (sigmoid' and
+//      the two W^T products as f16 GEMM outputs, ReLU masks); every Linear's
+//      f16 input and output gradient is stored neuron-major;
+//   2. the weight gradients as MFMA products over the sample axis, split over
+//      the samples into per-split partials;
+//   3. a fixed-order sum of the partials into the f32 gradients.
+// No float atomics anywhere: two runs give the same bits.
+//
+// Normal: -d sigma / d x in closed form, one thread per sample.
+#include "voxel_common.h"
+
+namespace dfhip {
+namespace vx {
+
+constexpr int kWaves = 8;     // forward
+constexpr int kBwdWaves = 4;  // gradient pass: twice the forward's register budget per wave
+constexpr uint32_t kChunk = 65536;  // samples per backward chunk
+constexpr uint32_t kSplits = 64;    // sample-axis splits of the weight-gradient products
+
+// ------------------------------------------------------------------ density only
+__global__ __launch_bounds__(256) void k_voxel_sigma(const float *__restrict__ xyz,
+                                                     const float *__restrict__ density, Geom G,
+                                                     float *__restrict__ sigma, uint32_t M) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= M) return;
+    const float x[3] = {xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2]};
+    const Cell c = locate(G, x);
+    float raw = 0.0f;
+    if (c.inside) raw = trilinear(corners(G, c), density, 1u, 0u);
+    sigma[i] = activate(raw, G.act_shift);
+}
+
+// ------------------------------------------------------------------ forward
+__global__ __launch_bounds__(64 * kWaves) void k_voxel_fwd(
+    const float *__restrict__ xyz, const float *__restrict__ density,
+    const float *__restrict__ k0, const float *__restrict__ view, Geom G, Ptrs P,
+    float *__restrict__ sigma, half_t *__restrict__ albedo, uint32_t M, uint32_t tiles) {
+    __shared__ FwdW W;
+    __shared__ __attribute__((aligned(16))) half_t xbuf[kWaves][16 * kLdI];
+    load_fwd_weights(W, P, G.dim0);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, c = lane & 15, h = lane >> 4;
+    const uint32_t waves = gridDim.x * kWaves;
+    for (uint32_t tile = blockIdx.x * kWaves + (threadIdx.x >> 6); tile < tiles; tile += waves) {
+        // weights are re-read from LDS every tile (hoisted out of the loop
+        // they spill; fieldmlp.hip's idiom)
+        asm volatile("" ::: "memory");
+        const uint32_t sample = tile * 16 + c;
+        const bool valid = sample < M;
+        float x[3] = {0.0f, 0.0f, 0.0f};
+        if (valid)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) x[d] = xyz[(size_t)sample * 3 + d];
+        const Cell cell = locate(G, x);
+        const bool inside = valid && cell.inside;
+        if (valid && h == 0) {
+            float raw = 0.0f;
+            if (inside) raw = trilinear(corners(G, cell), density, 1u, 0u);
+            sigma[sample] = activate(raw, G.act_shift);
+        }
+        float out[kOut] = {0.0f, 0.0f, 0.0f};
+        if (__ballot(inside) != 0ull) {  // wave-uniform
+            half8 xb[kSteps0];
+            feature_operands(G, cell, inside, k0, view, c, h, xbuf[threadIdx.x >> 6], xb);
+            half4 a1[kTiles], a2[kTiles];
+            mlp_tile(W, xb, c, h, a1, a2, out);
+        }
+        if (valid && h == 0)
+#pragma unroll
+            for (int k = 0; k < kOut; ++k)
+                albedo[(size_t)sample * 3 + k] = inside ? (half_t)sigmoidf(out[k]) : (half_t)0.5f;
+    }
+}
+
+// ------------------------------------------------------------------ gradient pass
+// The forward's images, the second layer transposed ([n_in][n_out]) and the
+// output layer as f32 of its f16 weights (its transposed product is three
+// FMAs per neuron).
+struct alignas(16) BwdW {
+    half_t w0[kHid * kLdI], w1[kHid * kLdH], w2[16 * kLdH];
+    float b0[kHid], b1[kHid], b2[16];
+    half_t w1t[kHid * kLdH];
+    float w2f[kOut][kHid];
+};
+
+__device__ inline void load_bwd_weights(BwdW &W, const Ptrs &P, uint32_t dim0) {
+    load_fwd_weights(*reinterpret_cast<FwdW *>(&W), P, dim0);
+    for (int i = threadIdx.x; i < kHid * kHid; i += blockDim.x)
+        W.w1t[(i % kHid) * kLdH + i / kHid] = (half_t)P.p[2][i];  // w[n_out][n_in]
+    for (int i = threadIdx.x; i < kOut * kHid; i += blockDim.x)
+        W.w2f[i / kHid][i % kHid] = (float)(half_t)P.p[4][i];
+}
+static_assert(offsetof(BwdW, w1t) == sizeof(FwdW), "BwdW starts with FwdW's members");
+
+// Rows of the neuron-major f16 images ([row][Mp], column = sample) the weight
+// gradients read: the feature row, both hidden activations, and the output
+// gradients of the three Linears.
+constexpr int kRowX = 0, kRowA1 = kRowX + kInPad, kRowA2 = kRowA1 + kHid, kRowG1 = kRowA2 + kHid,
+              kRowG2 = kRowG1 + kHid, kRowGo = kRowG2 + kHid, kRows = kRowGo + 8;
+
+template <typename ga_t>
+__global__ __launch_bounds__(64 * kBwdWaves) void k_voxel_bwd_act(
+    const float *__restrict__ xyz, const float *__restrict__ k0, const float *__restrict__ view,
+    Geom G, Ptrs P, const ga_t *__restrict__ grad_albedo, uint32_t M, uint32_t tiles, uint32_t Mp,
+    half_t *__restrict__ rows) {
+    __shared__ BwdW W;
+    __shared__ __attribute__((aligned(16))) half_t xbuf[kBwdWaves][16 * kLdI];
+    load_bwd_weights(W, P, G.dim0);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, c = lane & 15, h = lane >> 4;
+    const uint32_t waves = gridDim.x * kBwdWaves;
+    // tiles = Mp / 16: the padding rows of the last tile are written as zeros
+    for (uint32_t tile = blockIdx.x * kBwdWaves + (threadIdx.x >> 6); tile < tiles; tile += waves) {
+        asm volatile("" ::: "memory");  // no hoisting of the LDS operands (see k_voxel_fwd)
+        const uint32_t sample = tile * 16 + c;
+        const bool valid = sample < M;
+        float x[3] = {0.0f, 0.0f, 0.0f};
+        if (valid)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) x[d] = xyz[(size_t)sample * 3 + d];
+        const Cell cell = locate(G, x);
+        const bool inside = valid && cell.inside;
+        half8 xb[kSteps0];
+        feature_operands(G, cell, inside, k0, view, c, h, xbuf[threadIdx.x >> 6], xb);
+#pragma unroll
+        for (int s = 0; s < kSteps0; ++s)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                rows[(size_t)(kRowX + 32 * s + 8 * h + j) * Mp + sample] = xb[s][j];
+        half4 a1[kTiles], a2[kTiles];
+        float out[kOut];
+        mlp_tile(W, xb, c, h, a1, a2, out);
+        // ---- sigmoid backward in f16 on the f16 albedo; rows outside the box
+        // never reached the MLP: no gradient
+        half_t go[kOut];
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) {
+            float g = 0.0f;
+            if (inside) {
+                // the gradient of the f16 albedo arrives in f16
+                const float ga = (float)(half_t)(float)grad_albedo[(size_t)sample * 3 + k];
+                const float av = (float)(half_t)sigmoidf(out[k]);
+                g = ga * (1.0f - av) * av;
+            }
+            go[k] = (half_t)g;
+            if (h == 0) rows[(size_t)(kRowGo + k) * Mp + sample] = go[k];
+        }
+        // ---- dL/d(a2) = go @ W2 as an f16 GEMM output, ReLU mask
+        half4 g2[kTiles];
+#pragma unroll
+        for (int t = 0; t < kTiles; ++t) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n = 16 * t + 4 * h + r;
+                float s = (float)go[0] * W.w2f[0][n];
+                s = fmaf((float)go[1], W.w2f[1][n], s);
+                s = fmaf((float)go[2], W.w2f[2][n], s);
+                g2[t][r] = (float)a2[t][r] > 0.0f ? (half_t)s : (half_t)0.0f;
+                rows[(size_t)(kRowA2 + n) * Mp + sample] = a2[t][r];
+                rows[(size_t)(kRowG2 + n) * Mp + sample] = g2[t][r];
+            }
+        }
+        // ---- dL/d(a1) = g2 @ W1 as an f16 GEMM output, ReLU mask
+#pragma unroll
+        for (int t = 0; t < kTiles; ++t) {
+            f4 acc = f4{0, 0, 0, 0};
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                acc = mfma(a_perm(W.w1t, kLdH, 16 * t + c, s, h), b_tiles(g2, s), acc);
+            const half4 gh = __builtin_convertvector(acc, half4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n = 16 * t + 4 * h + r;
+                rows[(size_t)(kRowA1 + n) * Mp + sample] = a1[t][r];
+                rows[(size_t)(kRowG1 + n) * Mp + sample] =
+                    (float)a1[t][r] > 0.0f ? gh[r] : (half_t)0.0f;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------ weight gradients
+// One wave per (job, split): job = 16 output rows of one Linear against all of
+// its input columns, split = a range of 32-sample k-steps (resmlp.hip's
+// k_resmlp_wgrad).  A[i = c][k = 8 h + j] is the output gradient of row
+// row0 + c at samples 32 ks + 8 h + j, B[k][col = c] the input of column
+// 16 tm + c at the same samples; the bias is the product with a ones operand.
+// Jobs: 0..7 the first Linear, 8..15 the second, 16 the output layer.
+constexpr int kJobs = 17;
+
+__global__ __launch_bounds__(64) void k_voxel_wgrad(const half_t *__restrict__ rows, uint32_t Mp,
+                                                    uint32_t dim0, float *__restrict__ partial) {
+    const int job = blockIdx.x, lane = threadIdx.x, c = lane & 15, h = lane >> 4;
+    const uint32_t split = blockIdx.y, ksteps = Mp / 32u;
+    const uint32_t per = ceil_div(ksteps, (uint32_t)gridDim.y);
+    const uint32_t k0 = split * per < ksteps ? split * per : ksteps;
+    const uint32_t k1 = k0 + per < ksteps ? k0 + per : ksteps;
+    const half_t *Gr, *B;
+    int ntile, nrow, ld, tw, row0;  // column tiles, live rows, out stride (= columns), tensor
+    if (job < 8) {
+        row0 = 16 * job, Gr = rows + (size_t)kRowG1 * Mp, B = rows + (size_t)kRowX * Mp;
+        ntile = (int)ceil_div(dim0, 16u), nrow = 16, ld = (int)dim0, tw = 0;
+    } else if (job < 16) {
+        row0 = 16 * (job - 8), Gr = rows + (size_t)kRowG2 * Mp, B = rows + (size_t)kRowA1 * Mp;
+        ntile = kTiles, nrow = 16, ld = kHid, tw = 2;
+    } else {
+        row0 = 0, Gr = rows + (size_t)kRowGo * Mp, B = rows + (size_t)kRowA2 * Mp;
+        ntile = kTiles, nrow = kOut, ld = kHid, tw = 4;
+    }
+    f4 acc[kTiles + 1];
+#pragma unroll
+    for (int i = 0; i < kTiles + 1; ++i) acc[i] = f4{0, 0, 0, 0};
+    const half_t one = (half_t)1.0f;
+    const half8 ones8 = half8{one, one, one, one, one, one, one, one};
+    for (uint32_t ks = k0; ks < k1; ++ks) {
+        const size_t col = (size_t)32 * ks + 8 * h;
+        half8 a = half8{};
+        if (c < nrow) a = *reinterpret_cast<const half8 *>(Gr + (size_t)(row0 + c) * Mp + col);
+#pragma unroll
+        for (int tm = 0; tm < kTiles; ++tm)
+            if (tm < ntile)
+                acc[tm] = mfma(a, *reinterpret_cast<const half8 *>(B + (size_t)(16 * tm + c) * Mp + col),
+                               acc[tm]);
+        acc[kTiles] = mfma(a, ones8, acc[kTiles]);
+    }
+    // accumulator element r of lane (c, h): row 4 h + r, column c of the tile;
+    // every partial entry is written by exactly one lane of one job
+    float *out = partial + (size_t)split * t_offset(kTensors, dim0);
+    const uint32_t offw = t_offset(tw, dim0), offb = t_offset(tw + 1, dim0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = 4 * h + r;
+        if (row >= nrow) continue;
+#pragma unroll
+        for (int tm = 0; tm < kTiles; ++tm)
+            if (tm < ntile && 16 * tm + c < ld)
+                out[offw + (row0 + row) * ld + 16 * tm + c] = acc[tm][r];
+        if (c == 0) out[offb + row0 + row] = acc[kTiles][r];
+    }
+}
+
+// Fixed-order sums into the f32 gradients: a block takes 64 parameters; its
+// 16 part-lanes add the parts p = j, j + 16, ... in that order, then lane
+// j = 0 adds the 16 lane sums in order (as resmlp.hip's k_resmlp_reduce).
+__global__ __launch_bounds__(1024) void k_voxel_reduce(const float *__restrict__ partial,
+                                                       uint32_t splits, uint32_t dim0, GPtrs Gp,
+                                                       int accumulate) {
+    __shared__ float lane_sum[16][64];
+    const int col = threadIdx.x & 63, j = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * 64u + col, total = t_offset(kTensors, dim0);
+    int ti = 0;
+    uint32_t k = 0;
+    float s = 0.0f;
+    if (i < total) {
+        uint32_t off = 0;
+        for (int t = 0; t < kTensors; ++t) {
+            const uint32_t sz = t_size(t, dim0);
+            if (i >= off && i < off + sz) ti = t, k = i - off;
+            off += sz;
+        }
+        for (uint32_t p = j; p < splits; p += 16) s += partial[(size_t)p * total + i];
+    }
+    lane_sum[j][col] = s;
+    __syncthreads();
+    if (j != 0 || i >= total) return;
+    s = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += lane_sum[q][col];
+    float *dst = Gp.p[ti];
+    dst[k] = accumulate ? dst[k] + s : s;
+}
+
+// ------------------------------------------------------------------ normal
+__global__ __launch_bounds__(256) void k_voxel_normal(const float *__restrict__ xyz,
+                                                      const float *__restrict__ density, Geom G,
+                                                      float *__restrict__ normal, uint32_t M) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= M) return;
+    const float x[3] = {xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2]};
+    const Cell c = locate(G, x);
+    float n[3] = {0.0f, 0.0f, 0.0f};
+    if (c.inside) {
+        const Corners q = corners(G, c);
+        float v[8];  // corner k: bit 0 = z + 1, bit 1 = y + 1, bit 2 = x + 1
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = density[q.v[k]];
+        float raw = v[0] * q.w[0];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) raw = raw + v[k] * q.w[k];
+        // d raw / d g per grid axis: the weights' derivatives are -1 / +1 on
+        // the lower / upper corner (equal clamped corners cancel exactly)
+        float dg[3];
+        dg[2] = c.hi[1] * c.hi[0] * (v[1] - v[0]) + c.lo[1] * c.hi[0] * (v[3] - v[2]) +
+                c.hi[1] * c.lo[0] * (v[5] - v[4]) + c.lo[1] * c.lo[0] * (v[7] - v[6]);
+        dg[1] = c.hi[2] * c.hi[0] * (v[2] - v[0]) + c.lo[2] * c.hi[0] * (v[3] - v[1]) +
+                c.hi[2] * c.lo[0] * (v[6] - v[4]) + c.lo[2] * c.lo[0] * (v[7] - v[5]);
+        dg[0] = c.hi[2] * c.hi[1] * (v[4] - v[0]) + c.lo[2] * c.hi[1] * (v[5] - v[1]) +
+                c.hi[2] * c.lo[1] * (v[6] - v[2]) + c.lo[2] * c.lo[1] * (v[7] - v[3]);
+        // softplus backward (beta 1, threshold 20) of the gradient 10
+        const float y = raw + G.act_shift, z = expf(y);
+        const float ds = y > 20.0f ? 10.0f : 10.0f * z / (z + 1.0f);
+        float dp[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            float g = ds * dg[a];
+            g = g * (float)(G.n[a] - 1u) * 0.5f * 2.0f;
+            g = g / G.ext[a] * G.ext[a];
+            dp[a] = g * 1.25f * G.inv2b;
+        }
+        n[0] = -dp[0], n[1] = -dp[2], n[2] = -dp[1];  // grid y is world z
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) normal[(size_t)i * 3 + d] = n[d];
+}
+
+// ------------------------------------------------------------------ host side
+static uint32_t padded(uint32_t m) { return ceil_div(m, 32u) * 32u; }
+
+// scratch layout for a chunk of mp (padded) samples; both sizes are multiples
+// of 16 bytes
+struct Scratch {
+    size_t rows, partial, total;
+};
+static Scratch scratch_layout(uint32_t mp, uint32_t dim0) {
+    Scratch s;
+    size_t o = 0;
+    s.rows = o, o += (size_t)kRows * mp * sizeof(half_t);
+    s.partial = o, o += ceil_div((size_t)kSplits * t_offset(kTensors, dim0) * sizeof(float),
+                                 (size_t)16) * 16;
+    s.total = o;
+    return s;
+}
+
+static uint32_t persistent_blocks(uint32_t tiles, int waves) {
+    const uint32_t want = ceil_div(tiles, (uint32_t)waves), cus = device_cus();
+    const uint32_t n = want < cus ? want : cus;
+    return n ? n : 1u;
+}
+
+static bool geometry(const char *name, uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
+                     uint32_t pos_freqs, uint32_t view_dim, const float *box, float bound,
+                     float act_shift, bool colour, Geom &G) {
+    if (!box) {
+        set_error("%s: box is null", name);
+        return false;
+    }
+    if (!Nx || !Ny || !Nz || (uint64_t)Nx * Ny * Nz > 0x7fffffffull) {
+        set_error("%s: the volume must have 1 .. 2^31 - 1 voxels, got %u x %u x %u", name, Nx, Ny,
+                  Nz);
+        return false;
+    }
+    if (!(bound > 0.0f)) {
+        set_error("%s: bound must be positive", name);
+        return false;
+    }
+    G.bound = bound, G.inv2b = 1.0f / (2.0f * bound), G.act_shift = act_shift;
+    for (int a = 0; a < 3; ++a) {
+        G.mn[a] = box[a], G.mx[a] = box[3 + a], G.ext[a] = box[3 + a] - box[a];
+        if (!(G.ext[a] > 0.0f)) {
+            set_error("%s: box_max must exceed box_min on every axis", name);
+            return false;
+        }
+    }
+    G.n[0] = Nx, G.n[1] = Ny, G.n[2] = Nz;
+    G.C = C, G.P = pos_freqs, G.vdim = view_dim;
+    G.dim0 = C + (pos_freqs ? 3u + 6u * pos_freqs : 0u) + view_dim;
+    if (colour && (C == 0 || pos_freqs > 15u || view_dim > (uint32_t)kInPad ||
+                   G.dim0 > (uint32_t)kInPad)) {
+        set_error("%s: the feature row must have 1 .. %d entries with C >= 1 (C %u, pos_freqs %u, "
+                  "view_dim %u)", name, kInPad, C, pos_freqs, view_dim);
+        return false;
+    }
+    return true;
+}
+
+static bool gather(const char *name, const float *const *params, Ptrs &P) {
+    if (!params) {
+        set_error("%s: null parameter list", name);
+        return false;
+    }
+    for (int t = 0; t < kTensors; ++t) {
+        if (!params[t]) {
+            set_error("%s: parameter %d is null", name, t);
+            return false;
+        }
+        P.p[t] = params[t];
+    }
+    return true;
+}
+
+}  // namespace vx
+}  // namespace dfhip
+
+using namespace dfhip;
+using namespace dfhip::vx;
+
+extern "C" int dfhip_voxel_field_forward(const float *xyz, const float *density, const float *k0,
+                                         uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
+                                         uint32_t pos_freqs, const float *view, uint32_t view_dim,
+                                         const float *box, float bound, float act_shift,
+                                         const float *const *params, float *sigma, void *albedo,
+                                         uint32_t M, dfhip_stream_t stream) {
+    const char *name = "voxel_field_forward";
+    Geom G;
+    if (!geometry(name, Nx, Ny, Nz, C, pos_freqs, view_dim, box, bound, act_shift,
+                  albedo != nullptr, G))
+        return DFHIP_EINVAL;
+    Ptrs P = {};
+    if (albedo && !gather(name, params, P)) return DFHIP_EINVAL;
+    if (M == 0) return DFHIP_OK;
+    if (!xyz || !density || !sigma || (albedo && (!k0 || (view_dim && !view)))) {
+        set_error("%s: null pointer", name);
+        return DFHIP_EINVAL;
+    }
+    hipStream_t s = as_stream(stream);
+    if (!albedo) {
+        k_voxel_sigma<<<ceil_div(M, 256u), 256, 0, s>>>(xyz, density, G, sigma, M);
+        return check_launch(name);
+    }
+    const uint32_t tiles = ceil_div(M, 16u);
+    k_voxel_fwd<<<persistent_blocks(tiles, kWaves), 64 * kWaves, 0, s>>>(
+        xyz, density, k0, view, G, P, sigma, (half_t *)albedo, M, tiles);
+    return check_launch(name);
+}
+
+extern "C" uint64_t dfhip_voxel_field_backward_scratch(uint32_t M, uint32_t dim0) {
+    if (dim0 > (uint32_t)kInPad) dim0 = kInPad;
+    return (uint64_t)scratch_layout(padded(M < kChunk ? M : kChunk), dim0).total;
+}
+
+extern "C" int dfhip_voxel_field_backward(const float *xyz, const float *k0, uint32_t Nx,
+                                          uint32_t Ny, uint32_t Nz, uint32_t C,
+                                          uint32_t pos_freqs, const float *view,
+                                          uint32_t view_dim, const float *box, float bound,
+                                          const float *const *params, const void *grad_albedo,
+                                          int grad_albedo_dtype, uint32_t M, void *scratch,
+                                          float *const *grads, int accumulate,
+                                          dfhip_stream_t stream) {
+    const char *name = "voxel_field_backward";
+    Geom G;
+    if (!geometry(name, Nx, Ny, Nz, C, pos_freqs, view_dim, box, bound, 0.0f, true, G))
+        return DFHIP_EINVAL;
+    Ptrs P;
+    if (!gather(name, params, P)) return DFHIP_EINVAL;
+    GPtrs Gp;
+    if (!grads) {
+        set_error("%s: null gradient list", name);
+        return DFHIP_EINVAL;
+    }
+    for (int t = 0; t < kTensors; ++t) {
+        if (!grads[t]) {
+            set_error("%s: gradient %d is null", name, t);
+            return DFHIP_EINVAL;
+        }
+        Gp.p[t] = grads[t];
+    }
+    if (grad_albedo_dtype != DFHIP_F16 && grad_albedo_dtype != DFHIP_F32) {
+        set_error("%s: grad_albedo dtype must be f16 or f32", name);
+        return DFHIP_EDTYPE;
+    }
+    hipStream_t s = as_stream(stream);
+    if (M == 0) {
+        if (!accumulate)
+            for (int t = 0; t < kTensors; ++t)
+                (void)hipMemsetAsync(Gp.p[t], 0, t_size(t, G.dim0) * sizeof(float), s);
+        return check_launch(name);
+    }
+    if (!scratch || ((uintptr_t)scratch & 15u)) {
+        set_error("%s: scratch must be a 16-byte aligned buffer of "
+                  "dfhip_voxel_field_backward_scratch(M, dim0) bytes", name);
+        return DFHIP_EINVAL;
+    }
+    if (!xyz || !k0 || !grad_albedo || (view_dim && !view)) {
+        set_error("%s: null pointer", name);
+        return DFHIP_EINVAL;
+    }
+    char *base = (char *)scratch;
+    const size_t ga_size = grad_albedo_dtype == DFHIP_F16 ? 2 : 4;
+    const uint32_t total = t_offset(kTensors, G.dim0);
+    for (uint32_t m0 = 0; m0 < M; m0 += kChunk) {
+        const uint32_t m = M - m0 < kChunk ? M - m0 : kChunk;
+        const uint32_t mp = padded(m), tiles = mp / 16u;
+        const Scratch L = scratch_layout(mp, G.dim0);
+        half_t *rows = (half_t *)(base + L.rows);
+        float *partial = (float *)(base + L.partial);
+        const float *x = xyz + (size_t)m0 * 3;
+        const void *ga = (const char *)grad_albedo + (size_t)m0 * 3 * ga_size;
+        const uint32_t nblk = persistent_blocks(tiles, kBwdWaves);
+        if (grad_albedo_dtype == DFHIP_F16)
+            k_voxel_bwd_act<half_t><<<nblk, 64 * kBwdWaves, 0, s>>>(x, k0, view, G, P,
+                                                                (const half_t *)ga, m, tiles, mp,
+                                                                rows);
+        else
+            k_voxel_bwd_act<float><<<nblk, 64 * kBwdWaves, 0, s>>>(x, k0, view, G, P,
+                                                               (const float *)ga, m, tiles, mp,
+                                                               rows);
+        const uint32_t splits = mp / 32u < kSplits ? mp / 32u : kSplits;
+        k_voxel_wgrad<<<dim3(kJobs, splits), 64, 0, s>>>(rows, mp, G.dim0, partial);
+        k_voxel_reduce<<<ceil_div(total, 64u), 1024, 0, s>>>(partial, splits, G.dim0, Gp,
+                                                            (accumulate || m0 > 0) ? 1 : 0);
+    }
+    return check_launch(name);
+}
+
+extern "C" int dfhip_voxel_normal(const float *xyz, const float *density, uint32_t Nx,
+                                  uint32_t Ny, uint32_t Nz, const float *box, float bound,
+                                  float act_shift, float *normal, uint32_t M,
+                                  dfhip_stream_t stream) {
+    const char *name = "voxel_normal";
+    Geom G;
+    if (!geometry(name, Nx, Ny, Nz, 0u, 0u, 0u, box, bound, act_shift, false, G))
+        return DFHIP_EINVAL;
+    if (M == 0) return DFHIP_OK;
+    if (!xyz || !density || !normal) {
+        set_error("%s: null pointer", name);
+        return DFHIP_EINVAL;
+    }
+    k_voxel_normal<<<ceil_div(M, 256u), 256, 0, as_stream(stream)>>>(xyz, density, G, normal, M);
+    return check_launch(name);
+}

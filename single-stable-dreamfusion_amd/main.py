@@ -1,5 +1,5 @@
-"""Command line of the SDS trainer (mirror of reference main.py:12-162, grid
-and vanilla backbones).  Flag names and defaults are the reference's, because the whole
+"""Command line of the SDS trainer (mirror of reference main.py:12-162; grid,
+vanilla and dvgo backbones).  Flag names and defaults are the reference's, because the whole
 `opt` namespace is forwarded as renderer kwargs (utils.py:363)."""
 import argparse
 import os
@@ -43,7 +43,12 @@ def get_parser():
     # and SD-2.1-base guidance (text dim 1024); not in the reference
     p.add_argument("--bf16", action="store_true")
     p.add_argument("--sd_version", type=str, default="1.5", choices=["1.5", "2.1-base"])
-    p.add_argument("--backbone", type=str, default="grid")
+    p.add_argument("--backbone", type=str, default="grid", help="grid, vanilla or dvgo")
+    # the dvgo backbone (the reference hard-codes its checkpoint path, main.py:101-102)
+    p.add_argument("--dvgo_ckpt", type=str, default=None,
+                   help="--backbone dvgo: the pretrained DVGO checkpoint")
+    p.add_argument("--dvgo_alpha_init", type=float, default=None,
+                   help="--backbone dvgo: alpha_init when the checkpoint does not record it")
     p.add_argument("--w", type=int, default=64)
     p.add_argument("--h", type=int, default=64)
     p.add_argument("--jitter_pose", action="store_true")
@@ -87,12 +92,17 @@ def parse_opt(argv=None):
 
 
 def network_class(opt):
-    """The NeRFNetwork class of --backbone: `grid` (nerf/network_grid.py) or
-    `vanilla` (nerf/network.py)."""
+    """The NeRFNetwork class of --backbone: `grid` (nerf/network_grid.py),
+    `vanilla` (nerf/network.py) or `dvgo` (nerf/network_dvgo.py)."""
     if opt.backbone == "grid":
         from nerf.network_grid import NeRFNetwork
     elif opt.backbone == "vanilla":
         from nerf.network import NeRFNetwork
+    elif opt.backbone == "dvgo":
+        if not getattr(opt, "dvgo_ckpt", None):
+            raise ValueError("--backbone dvgo needs --dvgo_ckpt PATH (a pretrained DVGO "
+                             "checkpoint)")
+        from nerf.network_dvgo import NeRFNetwork
     else:
         raise NotImplementedError(f"--backbone {opt.backbone} is not implemented")
     return NeRFNetwork

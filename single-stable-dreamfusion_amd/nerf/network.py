@@ -15,8 +15,8 @@ heads, normal by autograd.grad), and so do shaded training steps, whose
 autograd normal carries a graph (through the Gaussian blob and trunc_exp).
 `native_calls` / `native_normal_calls` / `torch_calls` count which path ran.
 The persistent inference renderer and the native train step do not serve
-this backbone (native_infer_field / native_background_layers return None);
-the reference's NeRFNetwork_Kailu wrapper is not part of this package.
+this backbone (native_infer_field / native_background_layers return None).
+The reference's NeRFNetwork_Kailu wrapper of this file is nerf/network_dvgo.py.
 """
 import torch
 import torch.nn as nn

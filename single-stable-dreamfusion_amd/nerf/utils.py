@@ -518,6 +518,10 @@ class Trainer(object):
     def backward_only(self, loss):
         """The backward half of backward_and_step (captured in the step graph)."""
         scaled = self.scaler.scale(loss) if torch.is_tensor(loss) else None
+        if scaled is not None and not scaled.requires_grad:
+            # regularisers of sigma alone reach no parameter when the density
+            # is frozen (the dvgo backbone): nothing to back-propagate
+            scaled = None
         if self._pending_sds is not None:
             latents, grad = self._pending_sds
             self._pending_sds = None
