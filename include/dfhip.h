@@ -533,6 +533,55 @@ int dfhip_voxel_field_backward(const float *xyz, const float *k0, uint32_t Nx, u
 int dfhip_voxel_normal(const float *xyz, const float *density, uint32_t Nx, uint32_t Ny,
                        uint32_t Nz, const float *box, float bound, float act_shift,
                        float *normal, uint32_t M, dfhip_stream_t stream);
+/* nerf/renderer.py:496-532 with the voxel field above as the field: the DVGO
+ * backbone's inference frames in ONE persistent launch (csrc/voxelrender.hip),
+ * the voxel counterpart of dfhip_render_rays_infer_ordered further down, whose
+ * ray, march (bound .. T_thresh), order / chunk_log2 / tile_w, output and work
+ * arguments, queue layouts and retirement rules it shares; the field arguments
+ * (density .. params) are those of dfhip_voxel_field_forward, `bound` serving
+ * both.  Equal to the loop march_rays -> dfhip_voxel_field_forward ->
+ * composite_rays at n_step = 1 bit for bit (the same device functions in the
+ * same order; albedo f16, cast to f32 by the compositing).
+ * Out: weights_sum [N], depth [N], image [N,3] f32, every ray written once;
+ *      work: [4] uint32 scratch, words 1, 2 = the composited sample count.
+ * N = 0 clears work and launches nothing.  order NULL: pixel order. */
+int dfhip_voxel_render_rays_infer(uint32_t N, const float *rays_o, const float *rays_d,
+                                  const float *nears, const float *fars, const float *noises,
+                                  float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
+                                  uint32_t H, const uint8_t *grid, float T_thresh,
+                                  const float *density, const float *k0, uint32_t Nx,
+                                  uint32_t Ny, uint32_t Nz, uint32_t k0_channels,
+                                  uint32_t pos_freqs, const float *view, uint32_t view_dim,
+                                  const float *box, float act_shift,
+                                  const float *const *params, float *weights_sum, float *depth,
+                                  float *image, uint32_t *work, const int32_t *order,
+                                  uint32_t chunk_log2, uint32_t tile_w, dfhip_stream_t stream);
+/* The shaded frames of the same backbone (nerf/network.py:284-312 as the
+ * loop's field).  The normal is dfhip_voxel_normal's closed form from the
+ * sample's own cell, normalised as the module does (n / sqrt(max(|n|^2,
+ * 1e-20)), NaN -> 0, f32); the colours round where fp16 autocast rounds:
+ *   lambertian  = f16(ratio + f16((1 - ratio) clamp(f16(normal @ f16(light)), 0)))
+ *   TEXTURELESS colour = lambertian on all channels                   (f16)
+ *   LAMBERTIAN  colour = f16(albedo * lambertian)                     (f16)
+ *   NORMAL      colour = (normal + 1) / 2                             (f32)
+ * Density, depth and weights_sum are the albedo frame's bits.  TEXTURELESS and
+ * NORMAL read neither k0, view nor params (all may be NULL).  light: [3] f32
+ * (DEVICE), required; ratio: the ambient ratio.  Errors (DFHIP_EINVAL): NULL
+ * light, an unknown or the ALBEDO shading code, and those of the entry above. */
+int dfhip_voxel_render_rays_infer_shaded(uint32_t N, const float *rays_o, const float *rays_d,
+                                         const float *nears, const float *fars,
+                                         const float *noises, float bound, float dt_gamma,
+                                         uint32_t max_steps, uint32_t C, uint32_t H,
+                                         const uint8_t *grid, float T_thresh,
+                                         const float *density, const float *k0, uint32_t Nx,
+                                         uint32_t Ny, uint32_t Nz, uint32_t k0_channels,
+                                         uint32_t pos_freqs, const float *view,
+                                         uint32_t view_dim, const float *box, float act_shift,
+                                         const float *const *params, float *weights_sum,
+                                         float *depth, float *image, uint32_t *work,
+                                         const int32_t *order, uint32_t chunk_log2,
+                                         uint32_t tile_w, int shading, const float *light,
+                                         float ratio, dfhip_stream_t stream);
 
 /* Fused grid field (native path of nerf/field.py): tiled-grid encoding
  * (gridencoder.cu:75-178 arithmetic, f16 table) + the MLP/heads above in ONE

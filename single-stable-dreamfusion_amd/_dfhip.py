@@ -108,6 +108,13 @@ _SIGS = {
     "dfhip_voxel_field_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _f32,
                                    _vp, _vp, _i32, _u32, _vp, _vp, _i32, _vp],
     "dfhip_voxel_normal": [_vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32, _vp, _u32, _vp],
+    "dfhip_voxel_render_rays_infer": [_u32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32,
+                                      _vp, _f32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32,
+                                      _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp],
+    "dfhip_voxel_render_rays_infer_shaded": [_u32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32,
+                                             _u32, _vp, _f32, _vp, _vp, _u32, _u32, _u32, _u32,
+                                             _u32, _vp, _u32, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _u32, _u32, _i32, _vp, _f32, _vp],
     "dfhip_shading_stencil": [_vp, _vp, _u32, _f32, _f32, _vp, _vp, _vp],
     "dfhip_shading_forward": [_vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _u32, _vp, _vp, _vp,
                               _vp, _f32, _vp, _vp, _vp],

@@ -125,3 +125,65 @@ def normal(xyz, vol, bound, act_shift, out):
         raise RuntimeError("normal [M, 3] f32 expected")
     call("dfhip_voxel_normal", ptr(xyz), ptr(vol.density), *vol.n, vol.box, float(bound),
          float(act_shift), ptr(out), M, stream())
+
+
+# ---- fused inference render (march + voxel field + composite, persistent queue)
+
+SHADINGS = {"albedo": 0, "textureless": 1, "lambertian": 2, "normal": 3}  # dfhip_shading
+
+
+def render_rays_infer(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C, H,
+                      bitfield, T_thresh, vol, act_shift, params, weights_sum, depth, image, work,
+                      shading="albedo", light=None, ratio=1.0, order=None, chunk_log2=6, tile_w=0):
+    """Inference render of N rays of the DVGO backbone in one launch
+    (csrc/voxelrender.hip; dfhip_voxel_render_rays_infer, or its _shaded form
+    for shading "textureless" / "lambertian" / "normal").  rays_o / rays_d
+    [N, 3] f32, nears / fars [N] f32, noises [N] f32 or None, bitfield u8 (C
+    cascades of H^3 cells), vol: the checkpoint's Volume, params: the 6 rgbnet
+    tensors (None for the textureless and normal shadings, which read no
+    colour).  light: [3] f32 device tensor, ratio: the ambient ratio (shaded
+    frames).  Writes weights_sum [N], depth [N], image [N, 3] f32; work: [4]
+    int32 scratch whose words 1, 2 hold the evaluated sample count afterwards.
+    order / chunk_log2 / tile_w: the queue order of _fieldmlp.render_ray_order
+    (None: pixel order)."""
+    n = rays_o.shape[0]
+    for t, what, shp in ((rays_o, "rays_o", (n, 3)), (rays_d, "rays_d", (n, 3)),
+                         (nears, "nears", (n,)), (fars, "fars", (n,)),
+                         (weights_sum, "weights_sum", (n,)), (depth, "depth", (n,)),
+                         (image, "image", (n, 3))):
+        _f32(t, what)
+        if tuple(t.shape) != shp:
+            raise RuntimeError(f"{what} must have shape {shp}, got {tuple(t.shape)}")
+    if noises is not None:
+        _f32(noises, "noises")
+        if tuple(noises.shape) != (n,):
+            raise RuntimeError("noises must be [N]")
+    checked(bitfield, "bitfield", "u8")
+    if bitfield.numel() * 8 < C * H ** 3:
+        raise RuntimeError("bitfield is smaller than C * H^3 / 8 bytes")
+    checked(work, "work", "int")
+    if work.numel() < 4:
+        raise RuntimeError("work must hold 4 int32")
+    if order is not None:
+        checked(order, "order", "int")
+        if tuple(order.shape) != (-(-n // (1 << chunk_log2)),):
+            raise RuntimeError("order must be [ceil(N / 2^chunk_log2)] int32")
+    code = SHADINGS.get(shading, shading) if isinstance(shading, str) else shading
+    if isinstance(code, str):
+        raise RuntimeError(f"unknown shading {shading!r}")
+    colour = code in (0, 2)
+    pp = _pointers(params, vol.dim0, "param") if colour else None
+    args = (n, ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars), ptr(noises), float(bound),
+            float(dt_gamma), int(max_steps), int(C), int(H), ptr(bitfield), float(T_thresh),
+            ptr(vol.density), ptr(vol.k0), *vol.n, vol.C, vol.pos_freqs, ptr(vol.view),
+            vol.view_dim, vol.box, float(act_shift), pp, ptr(weights_sum), ptr(depth), ptr(image),
+            ptr(work), ptr(order), int(chunk_log2), int(tile_w))
+    if code == 0:
+        call("dfhip_voxel_render_rays_infer", *args, stream())
+        return
+    if light is not None:
+        _f32(light, "light")
+        if light.numel() != 3:
+            raise RuntimeError("light must hold 3 float32 values")
+    call("dfhip_voxel_render_rays_infer_shaded", *args, int(code), ptr(light), float(ratio),
+         stream())

@@ -139,6 +139,52 @@ __device__ __forceinline__ float activate(float raw, float act_shift) {
     return (y > 20.0f ? y : log1pf(expf(y))) * 10.0f;
 }
 
+// raw (the trilinear density sample, trilinear()'s sum) and n = -d sigma / d x
+// in world axes, not normalised, of a position inside the box: the closed
+// form of k_voxel_normal, from the cell's eight corner values.
+__device__ __forceinline__ void density_normal(const Geom &G, const Cell &c, const Corners &q,
+                                               const float *__restrict__ density, float &raw,
+                                               float (&n)[3]) {
+    float v[8];  // corner k: bit 0 = z + 1, bit 1 = y + 1, bit 2 = x + 1
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = density[q.v[k]];
+    raw = v[0] * q.w[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) raw = raw + v[k] * q.w[k];
+    // d raw / d g per grid axis: the weights' derivatives are -1 / +1 on
+    // the lower / upper corner (equal clamped corners cancel exactly)
+    float dg[3];
+    dg[2] = c.hi[1] * c.hi[0] * (v[1] - v[0]) + c.lo[1] * c.hi[0] * (v[3] - v[2]) +
+            c.hi[1] * c.lo[0] * (v[5] - v[4]) + c.lo[1] * c.lo[0] * (v[7] - v[6]);
+    dg[1] = c.hi[2] * c.hi[0] * (v[2] - v[0]) + c.lo[2] * c.hi[0] * (v[3] - v[1]) +
+            c.hi[2] * c.lo[0] * (v[6] - v[4]) + c.lo[2] * c.lo[0] * (v[7] - v[5]);
+    dg[0] = c.hi[2] * c.hi[1] * (v[4] - v[0]) + c.lo[2] * c.hi[1] * (v[5] - v[1]) +
+            c.hi[2] * c.lo[1] * (v[6] - v[2]) + c.lo[2] * c.lo[1] * (v[7] - v[3]);
+    // softplus backward (beta 1, threshold 20) of the gradient 10
+    const float y = raw + G.act_shift, z = expf(y);
+    const float ds = y > 20.0f ? 10.0f : 10.0f * z / (z + 1.0f);
+    float dp[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float g = ds * dg[a];
+        g = g * (float)(G.n[a] - 1u) * 0.5f * 2.0f;
+        g = g / G.ext[a] * G.ext[a];
+        dp[a] = g * 1.25f * G.inv2b;
+    }
+    n[0] = -dp[0], n[1] = -dp[2], n[2] = -dp[1];  // grid y is world z
+}
+
+// NeRFNetwork._unit: n / sqrt(clamp(|n|^2, 1e-20)), NaN -> 0 (f32).
+__device__ __forceinline__ void unit_normal(float (&n)[3]) {
+    const float ss = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+    const float r = sqrtf(fmaxf(ss, 1e-20f));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float q = n[a] / r;
+        n[a] = q != q ? 0.0f : q;
+    }
+}
+
 // Feature f of PE(u) = [u, sin(u_d 2^i), cos(u_d 2^i)] (d major), f32.
 __device__ __forceinline__ float pos_feature(const Geom &G, float u0, float u1, float u2,
                                              uint32_t f) {
@@ -256,6 +302,59 @@ __device__ __forceinline__ void mlp_tile(const WT &W, const half8 (&xb)[kSteps0]
     const half4 oh = __builtin_convertvector(o, half4);
 #pragma unroll
     for (int r = 0; r < kOut; ++r) out[r] = (float)oh[r];
+}
+
+// ---------------------------------------------------------------- host side
+// Argument checks shared by the entries of voxelfield.hip and voxelrender.hip.
+inline bool geometry(const char *name, uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
+                     uint32_t pos_freqs, uint32_t view_dim, const float *box, float bound,
+                     float act_shift, bool colour, Geom &G) {
+    if (!box) {
+        set_error("%s: box is null", name);
+        return false;
+    }
+    if (!Nx || !Ny || !Nz || (uint64_t)Nx * Ny * Nz > 0x7fffffffull) {
+        set_error("%s: the volume must have 1 .. 2^31 - 1 voxels, got %u x %u x %u", name, Nx, Ny,
+                  Nz);
+        return false;
+    }
+    if (!(bound > 0.0f)) {
+        set_error("%s: bound must be positive", name);
+        return false;
+    }
+    G.bound = bound, G.inv2b = 1.0f / (2.0f * bound), G.act_shift = act_shift;
+    for (int a = 0; a < 3; ++a) {
+        G.mn[a] = box[a], G.mx[a] = box[3 + a], G.ext[a] = box[3 + a] - box[a];
+        if (!(G.ext[a] > 0.0f)) {
+            set_error("%s: box_max must exceed box_min on every axis", name);
+            return false;
+        }
+    }
+    G.n[0] = Nx, G.n[1] = Ny, G.n[2] = Nz;
+    G.C = C, G.P = pos_freqs, G.vdim = view_dim;
+    G.dim0 = C + (pos_freqs ? 3u + 6u * pos_freqs : 0u) + view_dim;
+    if (colour && (C == 0 || pos_freqs > 15u || view_dim > (uint32_t)kInPad ||
+                   G.dim0 > (uint32_t)kInPad)) {
+        set_error("%s: the feature row must have 1 .. %d entries with C >= 1 (C %u, pos_freqs %u, "
+                  "view_dim %u)", name, kInPad, C, pos_freqs, view_dim);
+        return false;
+    }
+    return true;
+}
+
+inline bool gather(const char *name, const float *const *params, Ptrs &P) {
+    if (!params) {
+        set_error("%s: null parameter list", name);
+        return false;
+    }
+    for (int t = 0; t < kTensors; ++t) {
+        if (!params[t]) {
+            set_error("%s: parameter %d is null", name, t);
+            return false;
+        }
+        P.p[t] = params[t];
+    }
+    return true;
 }
 
 }  // namespace vx

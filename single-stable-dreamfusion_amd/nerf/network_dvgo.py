@@ -24,9 +24,18 @@ served natively for no-grad AND grad-enabled calls: the density volume is
 frozen and the positions are leaves, so the normal carries no graph to any
 trainable tensor and the closed form loses nothing (the vanilla backbone's
 normal does carry one, nerf/network.py).  `native_calls` /
-`native_normal_calls` / `torch_calls` count which path ran.  The persistent
-inference renderer and the native train step do not serve this backbone
-(native_infer_field / native_background_layers return None).
+`native_normal_calls` / `torch_calls` count which path ran.
+
+Eval frames (run_cuda without grad: --test, eval_step, test_step, test_gui)
+of the four shadings run as one persistent launch (csrc/voxelrender.hip)
+under the same conditions: native_infer_field returns the descriptor
+NeRFRenderer._infer_fused dispatches on, and `native_render_calls` counts the
+frames so rendered (each also counts once in `native_calls` and, shaded, in
+`native_normal_calls`: the native field served it, in one evaluation where
+the host loop makes one per iteration); `native_infer = False` returns to the
+host loop.  The
+native background head and the native train step do not serve this backbone
+(native_background_layers returns None).
 """
 import math
 
@@ -188,6 +197,8 @@ class NeRFNetwork(NeRFRenderer):
         self.fused_field = True
         # which path served common_forward / the normal
         self.native_calls = self.native_normal_calls = self.torch_calls = 0
+        # eval frames rendered by the fused persistent launch (csrc/voxelrender.hip)
+        self.native_render_calls = 0
         if self.bg_radius > 0:
             self.num_layers_bg = num_layers_bg
             self.hidden_dim_bg = hidden_dim_bg
@@ -307,6 +318,17 @@ class NeRFNetwork(NeRFRenderer):
         else:  # lambertian
             color = albedo * lambertian.unsqueeze(-1)
         return sigma, color, normal
+
+    def native_infer_field(self, shading, x):
+        """The voxel-field descriptor when the fused inference renderer serves
+        this frame: one of the four shadings, and the conditions of the
+        native field (fp16 autocast on the GPU, width 128, depth 3,
+        dim0 <= 96, fused_field); else None, and the host loop runs."""
+        if shading not in ("albedo", "textureless", "lambertian", "normal"):
+            return None
+        if not self._native(x):
+            return None
+        return _vf.InferField(self)
 
     def density(self, x):
         sigma, albedo = self.common_forward(x)

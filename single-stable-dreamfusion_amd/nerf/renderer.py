@@ -480,8 +480,10 @@ class NeRFRenderer(nn.Module):
         return None
 
     def native_infer_field(self, shading, x):
-        """(encoder, [Linear] * 3) when the fused inference renderer can evaluate
-        this field for `shading`, else None (subclass hook)."""
+        """The field's descriptor when the fused inference renderer can evaluate
+        it for `shading`, else None (subclass hook): (encoder, [Linear] * 3)
+        for the grid field, an object of kind "voxel" (voxel_field.InferField)
+        for the DVGO backbone."""
         return None
 
     def invalidate_infer_operands(self):
@@ -500,10 +502,12 @@ class NeRFRenderer(nn.Module):
         than albedo (textureless / lambertian / normal, network_grid.py:90-144)
         takes the shaded kernel, which evaluates each sample's
         finite-difference stencil in the same launch; light_d: [3] device
-        tensor, ambient_ratio: the ambient share."""
+        tensor, ambient_ratio: the ambient share.  A field descriptor of kind
+        "voxel" (nerf/voxel_field.py InferField, the DVGO backbone) takes
+        csrc/voxelrender.hip's launch instead; the queue order, the streams,
+        the noises and the accounting are shared."""
         import _fieldmlp
         import numpy as np
-        encoder, layers = field
         N = rays_o.shape[0]
         dev = rays_o.device
         weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
@@ -511,40 +515,54 @@ class NeRFRenderer(nn.Module):
         image = torch.empty(N, 3, dtype=torch.float32, device=dev)
         work = torch.empty(4, dtype=torch.int32, device=dev)
         noises = torch.rand(N, device=dev) if perturb else None
-        # the field's launch operands (f32 weights, the f16 table and its corner
-        # quads) are rebuilt only when a parameter changed: consecutive eval
-        # frames reuse them.  Tensor versions miss the native optimizer (a
-        # kernel writing through data_ptr, also inside a replayed graph), so
-        # the trainer bumps param_generation after every optimizer step and
-        # checkpoint load (invalidate_infer_operands)
-        params = [encoder.embeddings] + [p for lin in layers for p in (lin.weight, lin.bias)]
-        key = (self.__dict__.get("_param_generation", 0),
-               *((p.data_ptr(), p._version) for p in params))
-        cached = self.__dict__.get("_infer_operands")
-        if cached is None or cached[0] != key:
-            weights = []
-            for lin in layers:
-                weights += [lin.weight.detach().float().contiguous(),
-                            lin.bias.detach().float().contiguous()]
-            emb = encoder.embeddings.detach()
-            if self.infer_quads:
-                # the f16 cast and its corner quads in one launch (the field's
-                # gathers then take two 16-byte loads per level)
-                table = torch.empty(emb.shape, dtype=torch.half, device=dev)
-                quads = torch.empty(emb.shape[0], 4, dtype=torch.int32, device=dev)
-                _fieldmlp.grid_quads(emb.float().contiguous(), encoder.offsets,
-                                     float(np.log2(encoder.per_level_scale)),
-                                     int(encoder.base_resolution), encoder.gridtype_id,
-                                     bool(encoder.align_corners), table, quads)
-            else:
-                table, quads = emb.to(torch.half).contiguous(), None
-            cached = (key, weights, table, quads)
-            self.__dict__["_infer_operands"] = cached
-        _, weights, table, quads = cached
+        voxel = getattr(field, "kind", None) == "voxel"
+        if voxel:
+            # the DVGO backbone (csrc/voxelrender.hip): the frozen volumes' cached
+            # operands and rgbnet's own f32 parameters, read at launch (nothing
+            # is cast or copied, so nothing can go stale after a native
+            # optimizer step or a graph replay)
+            import _voxelfield
+            vol, act_shift, weights = field.operands()
+            field.launched(shading)
+            table = quads = None
+            field_bytes = 4 * (vol.density.numel() + vol.k0.numel())
+        else:
+            encoder, layers = field
+            # the field's launch operands (f32 weights, the f16 table and its corner
+            # quads) are rebuilt only when a parameter changed: consecutive eval
+            # frames reuse them.  Tensor versions miss the native optimizer (a
+            # kernel writing through data_ptr, also inside a replayed graph), so
+            # the trainer bumps param_generation after every optimizer step and
+            # checkpoint load (invalidate_infer_operands)
+            params = [encoder.embeddings] + [p for lin in layers for p in (lin.weight, lin.bias)]
+            key = (self.__dict__.get("_param_generation", 0),
+                   *((p.data_ptr(), p._version) for p in params))
+            cached = self.__dict__.get("_infer_operands")
+            if cached is None or cached[0] != key:
+                weights = []
+                for lin in layers:
+                    weights += [lin.weight.detach().float().contiguous(),
+                                lin.bias.detach().float().contiguous()]
+                emb = encoder.embeddings.detach()
+                if self.infer_quads:
+                    # the f16 cast and its corner quads in one launch (the field's
+                    # gathers then take two 16-byte loads per level)
+                    table = torch.empty(emb.shape, dtype=torch.half, device=dev)
+                    quads = torch.empty(emb.shape[0], 4, dtype=torch.int32, device=dev)
+                    _fieldmlp.grid_quads(emb.float().contiguous(), encoder.offsets,
+                                         float(np.log2(encoder.per_level_scale)),
+                                         int(encoder.base_resolution), encoder.gridtype_id,
+                                         bool(encoder.align_corners), table, quads)
+                else:
+                    table, quads = emb.to(torch.half).contiguous(), None
+                cached = (key, weights, table, quads)
+                self.__dict__["_infer_operands"] = cached
+            _, weights, table, quads = cached
+            field_bytes = table.numel() * 2
         import _dfhip
         # algorithmic bytes of the launch: rays in (o, d, near, far), outputs,
-        # the f16 table and the bitfield once
-        nbytes = N * (32 + 20) + table.numel() * 2 + self.density_bitfield.numel()
+        # the f16 table (or the f32 volumes) and the bitfield once
+        nbytes = N * (32 + 20) + field_bytes + self.density_bitfield.numel()
         # queue order: the chunks of 64 consecutive rays crossing the most of
         # the scene first (their rays do not then finish alone after the queue
         # ran dry: 0.38 -> 0.64 of the frame before it does)
@@ -575,24 +593,35 @@ class NeRFRenderer(nn.Module):
         rs = render_stream if render_stream is not None else main
         if rs is not main:  # the render on its own stream (beside a side-stream job)
             rs.wait_stream(main)
-        args = (*operands, noises, self.bound,
-                dt_gamma, max_steps, self.cascade, self.grid_size, self.density_bitfield,
-                T_thresh, table, encoder.offsets, float(np.log2(encoder.per_level_scale)),
-                int(encoder.base_resolution), encoder.gridtype_id, bool(encoder.align_corners),
-                weights, weights_sum, depth, image, work)
-        if shading == "albedo":
-            with torch.cuda.stream(rs), _dfhip.timed("render_rays_infer", nbytes):
-                _fieldmlp.render_rays_infer(*args, quads, order=order, chunk_log2=cl,
-                                            tile_w=tile_w)
+        if voxel:
+            # one entry for the four shadings (the shaded ones take light and ratio)
+            name = "voxel_render_rays_infer" + ("" if shading == "albedo" else "_shaded")
+            with torch.cuda.stream(rs), _dfhip.timed(name, nbytes + (0 if light is None else 12)):
+                _voxelfield.render_rays_infer(
+                    *operands, noises, self.bound, dt_gamma, max_steps, self.cascade,
+                    self.grid_size, self.density_bitfield, T_thresh, vol, act_shift, weights,
+                    weights_sum, depth, image, work, shading=shading, light=light,
+                    ratio=float(ambient_ratio), order=order, chunk_log2=cl, tile_w=tile_w)
         else:
-            # the same launch with seven field points per sample (csrc/render.hip)
-            with torch.cuda.stream(rs), _dfhip.timed("render_rays_infer_shaded", nbytes + 12):
-                _fieldmlp.render_rays_infer_shaded(*args, shading, light, float(ambient_ratio),
-                                                   1e-2, quads=quads, order=order,
-                                                   chunk_log2=cl, tile_w=tile_w)
+            args = (*operands, noises, self.bound,
+                    dt_gamma, max_steps, self.cascade, self.grid_size, self.density_bitfield,
+                    T_thresh, table, encoder.offsets, float(np.log2(encoder.per_level_scale)),
+                    int(encoder.base_resolution), encoder.gridtype_id, bool(encoder.align_corners),
+                    weights, weights_sum, depth, image, work)
+            if shading == "albedo":
+                with torch.cuda.stream(rs), _dfhip.timed("render_rays_infer", nbytes):
+                    _fieldmlp.render_rays_infer(*args, quads, order=order, chunk_log2=cl,
+                                                tile_w=tile_w)
+            else:
+                # the same launch with seven field points per sample (csrc/render.hip)
+                with torch.cuda.stream(rs), _dfhip.timed("render_rays_infer_shaded", nbytes + 12):
+                    _fieldmlp.render_rays_infer_shaded(*args, shading, light, float(ambient_ratio),
+                                                       1e-2, quads=quads, order=order,
+                                                       chunk_log2=cl, tile_w=tile_w)
         if rs is not main:
             main.wait_stream(rs)
-            for t in (*operands, weights_sum, depth, image, work, order, noises, table, quads,
+            field_tensors = (vol.density, vol.k0, vol.view) if voxel else (table, quads)
+            for t in (*operands, weights_sum, depth, image, work, order, noises, *field_tensors,
                       light, *weights):
                 if torch.is_tensor(t):
                     t.record_stream(rs)

@@ -132,3 +132,32 @@ def input_gradient(net, x):
     out = torch.empty(x.shape[0], 3, device=x.device, dtype=torch.float32)
     _voxelfield.normal(x, vol, float(net.bound), float(net.main_net.act_shift), out)
     return out
+
+
+class InferField:
+    """What NeRFRenderer._infer_fused needs to render this backbone in one
+    persistent launch (csrc/voxelrender.hip): the frozen volumes' cached
+    operands and rgbnet's f32 parameters themselves, taken when the frame is
+    launched, so an optimizer step between two frames (torch's, the native
+    Adam or a replayed graph, all of which write the parameters in place) is
+    seen by the next frame with no cache to invalidate."""
+    kind = "voxel"
+
+    def __init__(self, net):
+        self.net = net
+
+    def launched(self, shading):
+        """Count one fused frame: in native_render_calls, and as ONE native
+        evaluation of the field (shaded: and of the normal) for the whole
+        frame, where the host loop counts one per iteration."""
+        net = self.net
+        net.native_render_calls += 1
+        net.native_calls += 1
+        if shading != "albedo":
+            net.native_normal_calls += 1
+
+    def operands(self):
+        """(Volume, act_shift, the 6 rgbnet tensors in state_dict order)."""
+        m = self.net.main_net
+        vol, _ = volume(self.net)
+        return vol, float(m.act_shift), [p.detach() for p in rgbnet_params(m.rgbnet)]
