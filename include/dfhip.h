@@ -533,6 +533,84 @@ int dfhip_voxel_field_backward(const float *xyz, const float *k0, uint32_t Nx, u
 int dfhip_voxel_normal(const float *xyz, const float *density, uint32_t Nx, uint32_t Ny,
                        uint32_t Nz, const float *box, float bound, float act_shift,
                        float *normal, uint32_t M, dfhip_stream_t stream);
+/* Device-count forms of the three entries above (the DVGO backbone's native
+ * train step, nerf/native_voxel_step.py): the same arguments with M replaced
+ * by (cap, m_dev, align).  Buffers hold cap rows (cap < 2^31); the live count
+ * *m_dev (DEVICE int32, clamped to [0, cap]) is read by the kernels.  Launch
+ * shapes depend on cap only, no memset is decided on the host and nothing is
+ * read back, so the entries capture into a graph.  align >= 1; the effective
+ * row count is Me = min(cap, align_up(*m_dev, align)): align = 128 is the
+ * slice of march_rays_train, align = 1 the bare count.
+ * Forward and normal: rows [0, *m_dev) carry the host-count entry's bits; rows
+ * at or past the live count are neither read nor written (align is checked
+ * and otherwise unused).
+ * Backward: rows [0, *m_dev) of xyz and grad_albedo are read; rows
+ * [*m_dev, Me) act as padding rows (all zeros, never read).  The six gradients
+ * are bit-identical to dfhip_voxel_field_backward with M = Me on buffers whose
+ * rows [*m_dev, Me) hold position 0 and gradient 0: the same 65536-row chunks
+ * in order, min(mp / 32, 64) splits per chunk, the same fixed-order sums.
+ * Three launches whatever the count: the gradient pass over the live tiles,
+ * the weight gradients (a wave takes its split of every live chunk in turn),
+ * one reduction over the chunks in order.  *m_dev = 0 writes zero gradients
+ * from the kernel, or leaves them untouched with accumulate.
+ * scratch: dfhip_voxel_field_backward_dev_scratch(cap, dim0) bytes, 16-byte
+ * aligned: the neuron-major f16 images of every chunk of the capacity, 616
+ * rows x 2 bytes per sample (cap rounded up to 32), plus 64 partial images of
+ * the gradients per 65536-row chunk (64 x 4 x (128 dim0 + 17027) bytes each).
+ * At dim0 = 72 and max_steps 512: 64 x 64 rays, cap 2097152: 2,583,691,264 +
+ * 214,982,656 = 2,798,673,920 bytes; 128 x 128 rays, cap 8388608:
+ * 10,334,765,056 + 859,930,624 = 11,194,695,680 bytes. */
+int dfhip_voxel_field_forward_dev(const float *xyz, const float *density, const float *k0,
+                                  uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
+                                  uint32_t pos_freqs, const float *view, uint32_t view_dim,
+                                  const float *box, float bound, float act_shift,
+                                  const float *const *params, float *sigma, void *albedo,
+                                  uint32_t cap, const int32_t *m_dev, uint32_t align,
+                                  dfhip_stream_t stream);
+uint64_t dfhip_voxel_field_backward_dev_scratch(uint32_t cap, uint32_t dim0);
+int dfhip_voxel_field_backward_dev(const float *xyz, const float *k0, uint32_t Nx, uint32_t Ny,
+                                   uint32_t Nz, uint32_t C, uint32_t pos_freqs,
+                                   const float *view, uint32_t view_dim, const float *box,
+                                   float bound, const float *const *params,
+                                   const void *grad_albedo, int grad_albedo_dtype, uint32_t cap,
+                                   const int32_t *m_dev, uint32_t align, void *scratch,
+                                   float *const *grads, int accumulate, dfhip_stream_t stream);
+int dfhip_voxel_normal_dev(const float *xyz, const float *density, uint32_t Nx, uint32_t Ny,
+                           uint32_t Nz, const float *box, float bound, float act_shift,
+                           float *normal, uint32_t cap, const int32_t *m_dev, uint32_t align,
+                           dfhip_stream_t stream);
+/* Training shadings of the same backbone on capacity-sized buffers
+ * (csrc/voxelstep.hip; shading DFHIP_SHADING_TEXTURELESS or _LAMBERTIAN, any
+ * other code is DFHIP_EINVAL).  For rows [0, *m_dev), from xyz / dirs [cap, 3]
+ * f32, the density volume and, LAMBERTIAN only, albedo [cap, 3] f16 (may be
+ * NULL otherwise):
+ *   normal [cap, 3] f32 = dfhip_voxel_normal's closed form normalised as
+ *                         NeRFNetwork._unit (n / sqrt(max(|n|^2, 1e-20)), NaN -> 0)
+ *   lam    [cap]    f16 = the lambertian factor, rounded as
+ *                         dfhip_voxel_render_rays_infer_shaded documents it
+ *   color  [cap, 3] f16 = lam on all channels | f16(albedo * lam)
+ *   orient [1]      f32 = sum_i (1 - exp(-sigma_i)) clamp(normal_i . dirs_i, 0)^2
+ *                         / Me, Me = min(cap, align_up(*m_dev, align)): the
+ *                         mean over the march's slice, whose tail rows
+ *                         contribute 0 (0 when Me = 0); f32 terms, f64 sums
+ *                         in a fixed order, the f64 quotient rounded once.
+ * light: [3] f32 (DEVICE); ratio: the ambient ratio; partial:
+ * dfhip_shading_partial_doubles(cap) doubles of scratch.  Rows at or past the
+ * live count are neither read nor written.  Two launches.
+ * Backward: the density is frozen, so the normal carries no gradient;
+ * LAMBERTIAN writes grad_albedo [cap, 3] f16 = f16(grad_color * lam) on rows
+ * [0, *m_dev) (torch's half product: f32, rounded once), TEXTURELESS launches
+ * nothing. */
+int dfhip_voxel_shade_train_forward(const float *xyz, const float *dirs, const float *density,
+                                    uint32_t Nx, uint32_t Ny, uint32_t Nz, const float *box,
+                                    float bound, float act_shift, const void *albedo,
+                                    const float *light, float ratio, int shading, uint32_t cap,
+                                    const int32_t *m_dev, uint32_t align, float *normal,
+                                    void *lam, void *color, double *partial, float *orient,
+                                    dfhip_stream_t stream);
+int dfhip_voxel_shade_train_backward(const void *grad_color, const void *lam, int shading,
+                                     uint32_t cap, const int32_t *m_dev, uint32_t align,
+                                     void *grad_albedo, dfhip_stream_t stream);
 /* nerf/renderer.py:496-532 with the voxel field above as the field: the DVGO
  * backbone's inference frames in ONE persistent launch (csrc/voxelrender.hip),
  * the voxel counterpart of dfhip_render_rays_infer_ordered further down, whose

@@ -108,6 +108,15 @@ _SIGS = {
     "dfhip_voxel_field_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _f32,
                                    _vp, _vp, _i32, _u32, _vp, _vp, _i32, _vp],
     "dfhip_voxel_normal": [_vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32, _vp, _u32, _vp],
+    "dfhip_voxel_field_forward_dev": [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp,
+                                      _f32, _f32, _vp, _vp, _vp, _u32, _vp, _u32, _vp],
+    "dfhip_voxel_field_backward_dev": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp,
+                                       _f32, _vp, _vp, _i32, _u32, _vp, _u32, _vp, _vp, _i32, _vp],
+    "dfhip_voxel_normal_dev": [_vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32, _vp, _u32, _vp, _u32,
+                               _vp],
+    "dfhip_voxel_shade_train_forward": [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _f32, _f32, _vp, _vp,
+                                        _f32, _i32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dfhip_voxel_shade_train_backward": [_vp, _vp, _i32, _u32, _vp, _u32, _vp, _vp],
     "dfhip_voxel_render_rays_infer": [_u32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32,
                                       _vp, _f32, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32,
                                       _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp],
@@ -258,6 +267,8 @@ def load() -> ctypes.CDLL:
     lib.dfhip_resmlp_field_backward_scratch.argtypes = [_u32]
     lib.dfhip_voxel_field_backward_scratch.restype = ctypes.c_uint64
     lib.dfhip_voxel_field_backward_scratch.argtypes = [_u32, _u32]
+    lib.dfhip_voxel_field_backward_dev_scratch.restype = ctypes.c_uint64
+    lib.dfhip_voxel_field_backward_dev_scratch.argtypes = [_u32, _u32]
     lib.dfhip_ray_head_partial_floats.restype = _u32
     lib.dfhip_ray_head_partial_floats.argtypes = [_u32]
     lib.dfhip_grid_backward_partial_floats.restype = ctypes.c_uint64
@@ -281,7 +292,7 @@ def exported_symbols() -> list[str]:
             "dfhip_grid_backward_default_parts", "dfhip_grid_backward_partial_floats",
             "dfhip_field_mlp_params", "dfhip_field_mlp_backward_parts",
             "dfhip_resmlp_params", "dfhip_resmlp_field_backward_scratch",
-            "dfhip_voxel_field_backward_scratch",
+            "dfhip_voxel_field_backward_scratch", "dfhip_voxel_field_backward_dev_scratch",
             "dfhip_ray_head_partial_floats", "dfhip_march_rays_train_stage_floats",
             "dfhip_shading_partial_doubles", "dfhip_grid_backward_binned_tile",
             *_SIGS.keys()]

@@ -127,9 +127,144 @@ def normal(xyz, vol, bound, act_shift, out):
          float(act_shift), ptr(out), M, stream())
 
 
-# ---- fused inference render (march + voxel field + composite, persistent queue)
+# ---- device-count forms (the native train step: capacity-sized buffers, the
+# live row count in a device int32, launch shapes of the capacity only)
 
 SHADINGS = {"albedo": 0, "textureless": 1, "lambertian": 2, "normal": 3}  # dfhip_shading
+
+
+def backward_dev_scratch_bytes(cap, dim0):
+    """Bytes of field_backward_dev's scratch: 616 rows x 2 bytes per sample of
+    the capacity, plus 64 partial images of the gradients per 65536 rows."""
+    return int(_d.load().dfhip_voxel_field_backward_dev_scratch(int(cap), int(dim0)))
+
+
+def _count(m_dev, align):
+    checked(m_dev, "m_dev", "int")
+    if m_dev.numel() < 1:
+        raise RuntimeError("m_dev must hold the live row count (int32)")
+    if int(align) < 1:
+        raise RuntimeError("align must be at least 1")
+
+
+def field_forward_dev(xyz, vol, bound, act_shift, params, sigma, albedo, m_dev, align=1):
+    """field_forward on the rows [0, m_dev[0]) of capacity-sized buffers: xyz
+    [cap, 3], sigma [cap], albedo [cap, 3] f16 or None (density only); rows
+    at or past the live count are neither read nor written."""
+    cap = _positions(xyz)
+    _count(m_dev, align)
+    _f32(sigma, "sigma")
+    if tuple(sigma.shape) != (cap,):
+        raise RuntimeError("sigma [cap] f32 expected")
+    pp = None
+    if albedo is not None:
+        checked(albedo, "albedo")
+        if tuple(albedo.shape) != (cap, 3) or albedo.dtype != torch.float16:
+            raise RuntimeError("albedo [cap, 3] f16 expected")
+        pp = _pointers(params, vol.dim0, "param")
+    call("dfhip_voxel_field_forward_dev", ptr(xyz), ptr(vol.density), ptr(vol.k0), *vol.n, vol.C,
+         vol.pos_freqs, ptr(vol.view), vol.view_dim, vol.box, float(bound), float(act_shift), pp,
+         ptr(sigma), ptr(albedo), cap, ptr(m_dev), int(align), stream())
+
+
+def field_backward_dev(xyz, vol, bound, params, grad_albedo, grads, m_dev, align=1,
+                       accumulate=False, scratch=None):
+    """field_backward over min(cap, align_up(m_dev[0], align)) rows of
+    capacity-sized buffers, rows from the live count on taken as zero padding
+    (never read): the bits of field_backward on that many rows with zeroed
+    tail rows.  scratch: uint8 tensor of backward_dev_scratch_bytes(cap,
+    dim0) or None (allocated)."""
+    cap = _positions(xyz)
+    _count(m_dev, align)
+    checked(grad_albedo, "grad_albedo")
+    if grad_albedo.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("grad_albedo must be float16 or float32")
+    if tuple(grad_albedo.shape) != (cap, 3):
+        raise RuntimeError("grad_albedo [cap, 3] expected")
+    need = backward_dev_scratch_bytes(cap, vol.dim0)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=xyz.device)
+    checked(scratch, "scratch", "u8")
+    if scratch.numel() < need:
+        raise RuntimeError(f"scratch must hold {need} bytes")
+    call("dfhip_voxel_field_backward_dev", ptr(xyz), ptr(vol.k0), *vol.n, vol.C, vol.pos_freqs,
+         ptr(vol.view), vol.view_dim, vol.box, float(bound), _pointers(params, vol.dim0, "param"),
+         ptr(grad_albedo), _d.dtype_code(grad_albedo, "grad_albedo"), cap, ptr(m_dev), int(align),
+         ptr(scratch), _pointers(grads, vol.dim0, "grad"), int(bool(accumulate)), stream())
+
+
+def normal_dev(xyz, vol, bound, act_shift, out, m_dev, align=1):
+    """normal on the rows [0, m_dev[0]) of capacity-sized buffers."""
+    cap = _positions(xyz)
+    _count(m_dev, align)
+    _f32(out, "normal")
+    if tuple(out.shape) != (cap, 3):
+        raise RuntimeError("normal [cap, 3] f32 expected")
+    call("dfhip_voxel_normal_dev", ptr(xyz), ptr(vol.density), *vol.n, vol.box, float(bound),
+         float(act_shift), ptr(out), cap, ptr(m_dev), int(align), stream())
+
+
+def shade_partial_doubles(cap):
+    return int(_d.load().dfhip_shading_partial_doubles(int(cap)))
+
+
+def _half(t, what, shape):
+    checked(t, what)
+    if t.dtype != torch.float16 or tuple(t.shape) != shape:
+        raise RuntimeError(f"{what} {list(shape)} f16 expected")
+
+
+def shade_train_forward(xyz, dirs, vol, bound, act_shift, albedo, light, ratio, shading, m_dev,
+                        align, normal, lam, color, partial, orient):
+    """The textureless / lambertian colours of a train step on the rows
+    [0, m_dev[0]) of capacity-sized buffers (csrc/voxelstep.hip): writes the
+    unit normal [cap, 3] f32, the lambertian factor [cap] f16, the colour
+    [cap, 3] f16 and orient [1] f32, the orientation term's mean over
+    min(cap, align_up(m_dev[0], align)) rows.  albedo [cap, 3] f16 (lambertian;
+    else None), light [3] f32 on the device, partial:
+    shade_partial_doubles(cap) float64 of scratch."""
+    cap = _positions(xyz)
+    _count(m_dev, align)
+    code = SHADINGS.get(shading, shading) if isinstance(shading, str) else shading
+    if code not in (1, 2):
+        raise RuntimeError(f"shading must be textureless or lambertian, got {shading!r}")
+    for t, what in ((dirs, "dirs"), (normal, "normal")):
+        _f32(t, what)
+        if tuple(t.shape) != (cap, 3):
+            raise RuntimeError(f"{what} [cap, 3] f32 expected")
+    if code == 2:
+        _half(albedo, "albedo", (cap, 3))
+    _half(lam, "lam", (cap,))
+    _half(color, "color", (cap, 3))
+    _f32(light, "light")
+    _f32(orient, "orient")
+    if light.numel() != 3 or orient.numel() < 1:
+        raise RuntimeError("light [3] and orient [1] f32 expected")
+    checked(partial, "partial")
+    if partial.dtype != torch.float64 or partial.numel() < shade_partial_doubles(cap):
+        raise RuntimeError(f"partial must hold {shade_partial_doubles(cap)} float64")
+    call("dfhip_voxel_shade_train_forward", ptr(xyz), ptr(dirs), ptr(vol.density), *vol.n, vol.box,
+         float(bound), float(act_shift), ptr(albedo) if code == 2 else None, ptr(light),
+         float(ratio), int(code), cap, ptr(m_dev), int(align), ptr(normal), ptr(lam), ptr(color),
+         ptr(partial), ptr(orient), stream())
+
+
+def shade_train_backward(grad_color, lam, shading, m_dev, align, grad_albedo):
+    """grad_albedo [cap, 3] f16 = f16(grad_color * lam) on the live rows of a
+    lambertian step; a textureless step has no albedo gradient (no launch)."""
+    code = SHADINGS.get(shading, shading) if isinstance(shading, str) else shading
+    if code not in (1, 2):
+        raise RuntimeError(f"shading must be textureless or lambertian, got {shading!r}")
+    _count(m_dev, align)
+    cap = lam.shape[0]
+    _half(lam, "lam", (cap,))
+    _half(grad_color, "grad_color", (cap, 3))
+    _half(grad_albedo, "grad_albedo", (cap, 3))
+    call("dfhip_voxel_shade_train_backward", ptr(grad_color), ptr(lam), int(code), cap,
+         ptr(m_dev), int(align), ptr(grad_albedo), stream())
+
+
+# ---- fused inference render (march + voxel field + composite, persistent queue)
 
 
 def render_rays_infer(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C, H,

@@ -40,10 +40,32 @@ constexpr int kBwdWaves = 4;  // gradient pass: twice the forward's register bud
 constexpr uint32_t kChunk = 65536;  // samples per backward chunk
 constexpr uint32_t kSplits = 64;    // sample-axis splits of the weight-gradient products
 
+// ------------------------------------------------------------------ device counts
+// The kDev instances of the kernels below take their row count from the
+// device: M is then the capacity of the buffers and *m_dev the live count, so
+// the launch shape depends on the capacity only and the launches capture into
+// a graph.  Rows at or past the live count are neither read nor written.
+__device__ __forceinline__ uint32_t live_rows(const int32_t *m_dev, uint32_t cap) {
+    const int32_t m = *m_dev;
+    return m < 0 ? 0u : ((uint32_t)m < cap ? (uint32_t)m : cap);
+}
+
+// Rows the backward sums over: the live count rounded up to `align` (the
+// march's slice), at most the capacity.
+__device__ __forceinline__ uint32_t effective_rows(uint32_t m, uint32_t cap, uint32_t align) {
+    const uint64_t a = ((uint64_t)m + align - 1u) / align * align;
+    return a < (uint64_t)cap ? (uint32_t)a : cap;
+}
+
+__host__ __device__ inline uint32_t padded(uint32_t m) { return ceil_div(m, 32u) * 32u; }
+
 // ------------------------------------------------------------------ density only
+template <bool kDev>
 __global__ __launch_bounds__(256) void k_voxel_sigma(const float *__restrict__ xyz,
                                                      const float *__restrict__ density, Geom G,
-                                                     float *__restrict__ sigma, uint32_t M) {
+                                                     float *__restrict__ sigma, uint32_t M,
+                                                     const int32_t *__restrict__ m_dev) {
+    if constexpr (kDev) M = live_rows(m_dev, M);
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= M) return;
     const float x[3] = {xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2]};
@@ -54,9 +76,10 @@ __global__ __launch_bounds__(256) void k_voxel_sigma(const float *__restrict__ x
 }
 
 // ------------------------------------------------------------------ forward
-__global__ __launch_bounds__(64 * kWaves) void k_voxel_fwd(
+// (the body of both kernels below: the host-count one keeps its argument list)
+__device__ __forceinline__ void voxel_fwd(
     const float *__restrict__ xyz, const float *__restrict__ density,
-    const float *__restrict__ k0, const float *__restrict__ view, Geom G, Ptrs P,
+    const float *__restrict__ k0, const float *__restrict__ view, const Geom &G, const Ptrs &P,
     float *__restrict__ sigma, half_t *__restrict__ albedo, uint32_t M, uint32_t tiles) {
     __shared__ FwdW W;
     __shared__ __attribute__((aligned(16))) half_t xbuf[kWaves][16 * kLdI];
@@ -95,6 +118,23 @@ __global__ __launch_bounds__(64 * kWaves) void k_voxel_fwd(
     }
 }
 
+__global__ __launch_bounds__(64 * kWaves) void k_voxel_fwd(
+    const float *__restrict__ xyz, const float *__restrict__ density,
+    const float *__restrict__ k0, const float *__restrict__ view, Geom G, Ptrs P,
+    float *__restrict__ sigma, half_t *__restrict__ albedo, uint32_t M, uint32_t tiles) {
+    voxel_fwd(xyz, density, k0, view, G, P, sigma, albedo, M, tiles);
+}
+
+// Device count: `cap` rows of buffers, the tiles of the live rows.
+__global__ __launch_bounds__(64 * kWaves) void k_voxel_fwd_dev(
+    const float *__restrict__ xyz, const float *__restrict__ density,
+    const float *__restrict__ k0, const float *__restrict__ view, Geom G, Ptrs P,
+    float *__restrict__ sigma, half_t *__restrict__ albedo, uint32_t cap,
+    const int32_t *__restrict__ m_dev) {
+    const uint32_t M = live_rows(m_dev, cap);
+    voxel_fwd(xyz, density, k0, view, G, P, sigma, albedo, M, ceil_div(M, 16u));
+}
+
 // ------------------------------------------------------------------ gradient pass
 // The forward's images, the second layer transposed ([n_in][n_out]) and the
 // output layer as f32 of its f16 weights (its transposed product is three
@@ -121,11 +161,21 @@ static_assert(offsetof(BwdW, w1t) == sizeof(FwdW), "BwdW starts with FwdW's memb
 constexpr int kRowX = 0, kRowA1 = kRowX + kInPad, kRowA2 = kRowA1 + kHid, kRowG1 = kRowA2 + kHid,
               kRowG2 = kRowG1 + kHid, kRowGo = kRowG2 + kHid, kRows = kRowGo + 8;
 
-template <typename ga_t>
+// kDev: M is the capacity.  Rows [0, live) are read; the tiles up to the
+// padded effective count are written, rows from the live count on as padding
+// rows (zero output gradients).  Chunk c of 65536 samples has its images at
+// rows + kRows * kChunk * c with the row stride of the capacity's chunk c, so
+// the layout depends on the capacity only.
+template <typename ga_t, bool kDev>
 __global__ __launch_bounds__(64 * kBwdWaves) void k_voxel_bwd_act(
     const float *__restrict__ xyz, const float *__restrict__ k0, const float *__restrict__ view,
     Geom G, Ptrs P, const ga_t *__restrict__ grad_albedo, uint32_t M, uint32_t tiles, uint32_t Mp,
-    half_t *__restrict__ rows) {
+    half_t *__restrict__ rows, const int32_t *__restrict__ m_dev, uint32_t align) {
+    const uint32_t cap = M;
+    if constexpr (kDev) {
+        M = live_rows(m_dev, cap);
+        tiles = padded(effective_rows(M, cap, align)) / 16u;
+    }
     __shared__ BwdW W;
     __shared__ __attribute__((aligned(16))) half_t xbuf[kBwdWaves][16 * kLdI];
     load_bwd_weights(W, P, G.dim0);
@@ -137,6 +187,15 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_voxel_bwd_act(
         asm volatile("" ::: "memory");  // no hoisting of the LDS operands (see k_voxel_fwd)
         const uint32_t sample = tile * 16 + c;
         const bool valid = sample < M;
+        // the images of this tile: [row][ld], column col
+        half_t *rw = rows;
+        uint32_t ld = Mp, col = sample;
+        if constexpr (kDev) {
+            const uint32_t chunk = (tile * 16u) / kChunk, left = cap - chunk * kChunk;
+            rw = rows + (size_t)kRows * kChunk * chunk;
+            ld = padded(left < kChunk ? left : kChunk);
+            col = sample - chunk * kChunk;
+        }
         float x[3] = {0.0f, 0.0f, 0.0f};
         if (valid)
 #pragma unroll
@@ -149,7 +208,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_voxel_bwd_act(
         for (int s = 0; s < kSteps0; ++s)
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                rows[(size_t)(kRowX + 32 * s + 8 * h + j) * Mp + sample] = xb[s][j];
+                rw[(size_t)(kRowX + 32 * s + 8 * h + j) * ld + col] = xb[s][j];
         half4 a1[kTiles], a2[kTiles];
         float out[kOut];
         mlp_tile(W, xb, c, h, a1, a2, out);
@@ -166,7 +225,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_voxel_bwd_act(
                 g = ga * (1.0f - av) * av;
             }
             go[k] = (half_t)g;
-            if (h == 0) rows[(size_t)(kRowGo + k) * Mp + sample] = go[k];
+            if (h == 0) rw[(size_t)(kRowGo + k) * ld + col] = go[k];
         }
         // ---- dL/d(a2) = go @ W2 as an f16 GEMM output, ReLU mask
         half4 g2[kTiles];
@@ -179,8 +238,8 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_voxel_bwd_act(
                 s = fmaf((float)go[1], W.w2f[1][n], s);
                 s = fmaf((float)go[2], W.w2f[2][n], s);
                 g2[t][r] = (float)a2[t][r] > 0.0f ? (half_t)s : (half_t)0.0f;
-                rows[(size_t)(kRowA2 + n) * Mp + sample] = a2[t][r];
-                rows[(size_t)(kRowG2 + n) * Mp + sample] = g2[t][r];
+                rw[(size_t)(kRowA2 + n) * ld + col] = a2[t][r];
+                rw[(size_t)(kRowG2 + n) * ld + col] = g2[t][r];
             }
         }
         // ---- dL/d(a1) = g2 @ W1 as an f16 GEMM output, ReLU mask
@@ -194,8 +253,8 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_voxel_bwd_act(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int n = 16 * t + 4 * h + r;
-                rows[(size_t)(kRowA1 + n) * Mp + sample] = a1[t][r];
-                rows[(size_t)(kRowG1 + n) * Mp + sample] =
+                rw[(size_t)(kRowA1 + n) * ld + col] = a1[t][r];
+                rw[(size_t)(kRowG1 + n) * ld + col] =
                     (float)a1[t][r] > 0.0f ? gh[r] : (half_t)0.0f;
             }
         }
@@ -211,11 +270,14 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_voxel_bwd_act(
 // Jobs: 0..7 the first Linear, 8..15 the second, 16 the output layer.
 constexpr int kJobs = 17;
 
-__global__ __launch_bounds__(64) void k_voxel_wgrad(const half_t *__restrict__ rows, uint32_t Mp,
-                                                    uint32_t dim0, float *__restrict__ partial) {
+// One chunk's product of wave (job, split) out of `splits`: images of row
+// stride Mp, mp / 32 k-steps.
+__device__ __forceinline__ void wgrad_chunk(const half_t *__restrict__ rows, uint32_t Mp,
+                                            uint32_t mp, uint32_t split, uint32_t splits,
+                                            uint32_t dim0, float *__restrict__ partial) {
     const int job = blockIdx.x, lane = threadIdx.x, c = lane & 15, h = lane >> 4;
-    const uint32_t split = blockIdx.y, ksteps = Mp / 32u;
-    const uint32_t per = ceil_div(ksteps, (uint32_t)gridDim.y);
+    const uint32_t ksteps = mp / 32u;
+    const uint32_t per = ceil_div(ksteps, splits);
     const uint32_t k0 = split * per < ksteps ? split * per : ksteps;
     const uint32_t k1 = k0 + per < ksteps ? k0 + per : ksteps;
     const half_t *Gr, *B;
@@ -262,6 +324,43 @@ __global__ __launch_bounds__(64) void k_voxel_wgrad(const half_t *__restrict__ r
     }
 }
 
+__global__ __launch_bounds__(64) void k_voxel_wgrad(const half_t *__restrict__ rows, uint32_t Mp,
+                                                    uint32_t dim0, float *__restrict__ partial) {
+    wgrad_chunk(rows, Mp, Mp, blockIdx.y, gridDim.y, dim0, partial);
+}
+
+// The chunks of the device-count backward: m0, the padded row count and the
+// splits of chunk `chunk` of Me effective rows (the host loop's values), the
+// row stride of its images (the capacity's).
+struct Chunk {
+    uint32_t mp, splits, ld;
+};
+__device__ __forceinline__ Chunk chunk_of(uint32_t chunk, uint32_t Me, uint32_t cap) {
+    const uint32_t m0 = chunk * kChunk, left = cap - m0;
+    Chunk k;
+    k.mp = padded(Me - m0 < kChunk ? Me - m0 : kChunk);
+    k.splits = k.mp / 32u < kSplits ? k.mp / 32u : kSplits;
+    k.ld = padded(left < kChunk ? left : kChunk);
+    return k;
+}
+
+// Device count: wave (job, split) takes its share of every live chunk in turn;
+// chunk c has kSplits partial images at partial + c * kSplits * total.
+__global__ __launch_bounds__(64) void k_voxel_wgrad_dev(const half_t *__restrict__ rows,
+                                                        uint32_t cap,
+                                                        const int32_t *__restrict__ m_dev,
+                                                        uint32_t align, uint32_t dim0,
+                                                        float *__restrict__ partial) {
+    const uint32_t Me = effective_rows(live_rows(m_dev, cap), cap, align);
+    const size_t total = t_offset(kTensors, dim0);
+    for (uint32_t chunk = 0; chunk * kChunk < Me; ++chunk) {
+        const Chunk k = chunk_of(chunk, Me, cap);
+        if (blockIdx.y >= k.splits) continue;
+        wgrad_chunk(rows + (size_t)kRows * kChunk * chunk, k.ld, k.mp, blockIdx.y, k.splits, dim0,
+                    partial + (size_t)chunk * kSplits * total);
+    }
+}
+
 // Fixed-order sums into the f32 gradients: a block takes 64 parameters; its
 // 16 part-lanes add the parts p = j, j + 16, ... in that order, then lane
 // j = 0 adds the 16 lane sums in order (as resmlp.hip's k_resmlp_reduce).
@@ -293,10 +392,58 @@ __global__ __launch_bounds__(1024) void k_voxel_reduce(const float *__restrict__
     dst[k] = accumulate ? dst[k] + s : s;
 }
 
+// Device count: the chunks' sums in chunk order, each formed as above and
+// added to the running f32 value as the host loop's launches add it in memory.
+// No live chunk: zeros, or nothing with accumulate.
+__global__ __launch_bounds__(1024) void k_voxel_reduce_dev(const float *__restrict__ partial,
+                                                           uint32_t cap,
+                                                           const int32_t *__restrict__ m_dev,
+                                                           uint32_t align, uint32_t dim0, GPtrs Gp,
+                                                           int accumulate) {
+    __shared__ float lane_sum[16][64];
+    const uint32_t Me = effective_rows(live_rows(m_dev, cap), cap, align);
+    const int col = threadIdx.x & 63, j = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * 64u + col, total = t_offset(kTensors, dim0);
+    int ti = 0;
+    uint32_t k = 0;
+    if (i < total) {
+        uint32_t off = 0;
+        for (int t = 0; t < kTensors; ++t) {
+            const uint32_t sz = t_size(t, dim0);
+            if (i >= off && i < off + sz) ti = t, k = i - off;
+            off += sz;
+        }
+    }
+    const bool writer = j == 0 && i < total;
+    float *dst = Gp.p[ti];
+    float v = 0.0f;
+    if (writer && accumulate) v = dst[k];
+    for (uint32_t chunk = 0; chunk * kChunk < Me; ++chunk) {  // block-uniform
+        const uint32_t splits = chunk_of(chunk, Me, cap).splits;
+        const float *part = partial + (size_t)chunk * kSplits * total;
+        float s = 0.0f;
+        if (i < total)
+            for (uint32_t p = j; p < splits; p += 16) s += part[(size_t)p * total + i];
+        lane_sum[j][col] = s;
+        __syncthreads();
+        if (writer) {
+            s = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) s += lane_sum[q][col];
+            v = (accumulate || chunk > 0) ? v + s : s;
+        }
+        __syncthreads();  // lane_sum is rewritten next
+    }
+    if (writer && !(accumulate && Me == 0)) dst[k] = v;
+}
+
 // ------------------------------------------------------------------ normal
+template <bool kDev>
 __global__ __launch_bounds__(256) void k_voxel_normal(const float *__restrict__ xyz,
                                                       const float *__restrict__ density, Geom G,
-                                                      float *__restrict__ normal, uint32_t M) {
+                                                      float *__restrict__ normal, uint32_t M,
+                                                      const int32_t *__restrict__ m_dev) {
+    if constexpr (kDev) M = live_rows(m_dev, M);
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= M) return;
     const float x[3] = {xyz[(size_t)i * 3], xyz[(size_t)i * 3 + 1], xyz[(size_t)i * 3 + 2]};
@@ -311,8 +458,6 @@ __global__ __launch_bounds__(256) void k_voxel_normal(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------ host side
-static uint32_t padded(uint32_t m) { return ceil_div(m, 32u) * 32u; }
-
 // scratch layout for a chunk of mp (padded) samples; both sizes are multiples
 // of 16 bytes
 struct Scratch {
@@ -340,13 +485,13 @@ static uint32_t persistent_blocks(uint32_t tiles, int waves) {
 using namespace dfhip;
 using namespace dfhip::vx;
 
-extern "C" int dfhip_voxel_field_forward(const float *xyz, const float *density, const float *k0,
-                                         uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
-                                         uint32_t pos_freqs, const float *view, uint32_t view_dim,
-                                         const float *box, float bound, float act_shift,
-                                         const float *const *params, float *sigma, void *albedo,
-                                         uint32_t M, dfhip_stream_t stream) {
-    const char *name = "voxel_field_forward";
+// m_dev NULL: M rows; else M is the capacity and *m_dev the live count
+static int field_forward(const char *name, const float *xyz, const float *density,
+                         const float *k0, uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
+                         uint32_t pos_freqs, const float *view, uint32_t view_dim,
+                         const float *box, float bound, float act_shift,
+                         const float *const *params, float *sigma, void *albedo, uint32_t M,
+                         const int32_t *m_dev, dfhip_stream_t stream) {
     Geom G;
     if (!geometry(name, Nx, Ny, Nz, C, pos_freqs, view_dim, box, bound, act_shift,
                   albedo != nullptr, G))
@@ -360,13 +505,63 @@ extern "C" int dfhip_voxel_field_forward(const float *xyz, const float *density,
     }
     hipStream_t s = as_stream(stream);
     if (!albedo) {
-        k_voxel_sigma<<<ceil_div(M, 256u), 256, 0, s>>>(xyz, density, G, sigma, M);
+        if (m_dev)
+            k_voxel_sigma<true><<<ceil_div(M, 256u), 256, 0, s>>>(xyz, density, G, sigma, M, m_dev);
+        else
+            k_voxel_sigma<false><<<ceil_div(M, 256u), 256, 0, s>>>(xyz, density, G, sigma, M,
+                                                                   nullptr);
         return check_launch(name);
     }
     const uint32_t tiles = ceil_div(M, 16u);
-    k_voxel_fwd<<<persistent_blocks(tiles, kWaves), 64 * kWaves, 0, s>>>(
-        xyz, density, k0, view, G, P, sigma, (half_t *)albedo, M, tiles);
+    if (m_dev)
+        k_voxel_fwd_dev<<<persistent_blocks(tiles, kWaves), 64 * kWaves, 0, s>>>(
+            xyz, density, k0, view, G, P, sigma, (half_t *)albedo, M, m_dev);
+    else
+        k_voxel_fwd<<<persistent_blocks(tiles, kWaves), 64 * kWaves, 0, s>>>(
+            xyz, density, k0, view, G, P, sigma, (half_t *)albedo, M, tiles);
     return check_launch(name);
+}
+
+// The checks of the device-count forms' own arguments.
+static bool device_count(const char *name, uint32_t cap, const int32_t *m_dev, uint32_t align) {
+    if (cap > 0x7fffffffu) {
+        set_error("%s: the capacity must be below 2^31 rows, got %u", name, cap);
+        return false;
+    }
+    if (!m_dev) {
+        set_error("%s: m_dev is null", name);
+        return false;
+    }
+    if (align == 0) {
+        set_error("%s: align must be at least 1", name);
+        return false;
+    }
+    return true;
+}
+
+extern "C" int dfhip_voxel_field_forward(const float *xyz, const float *density, const float *k0,
+                                         uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
+                                         uint32_t pos_freqs, const float *view, uint32_t view_dim,
+                                         const float *box, float bound, float act_shift,
+                                         const float *const *params, float *sigma, void *albedo,
+                                         uint32_t M, dfhip_stream_t stream) {
+    return field_forward("voxel_field_forward", xyz, density, k0, Nx, Ny, Nz, C, pos_freqs, view,
+                         view_dim, box, bound, act_shift, params, sigma, albedo, M, nullptr,
+                         stream);
+}
+
+extern "C" int dfhip_voxel_field_forward_dev(const float *xyz, const float *density,
+                                             const float *k0, uint32_t Nx, uint32_t Ny,
+                                             uint32_t Nz, uint32_t C, uint32_t pos_freqs,
+                                             const float *view, uint32_t view_dim,
+                                             const float *box, float bound, float act_shift,
+                                             const float *const *params, float *sigma,
+                                             void *albedo, uint32_t cap, const int32_t *m_dev,
+                                             uint32_t align, dfhip_stream_t stream) {
+    const char *name = "voxel_field_forward_dev";
+    if (!device_count(name, cap, m_dev, align)) return DFHIP_EINVAL;
+    return field_forward(name, xyz, density, k0, Nx, Ny, Nz, C, pos_freqs, view, view_dim, box,
+                         bound, act_shift, params, sigma, albedo, cap, m_dev, stream);
 }
 
 extern "C" uint64_t dfhip_voxel_field_backward_scratch(uint32_t M, uint32_t dim0) {
@@ -374,21 +569,31 @@ extern "C" uint64_t dfhip_voxel_field_backward_scratch(uint32_t M, uint32_t dim0
     return (uint64_t)scratch_layout(padded(M < kChunk ? M : kChunk), dim0).total;
 }
 
-extern "C" int dfhip_voxel_field_backward(const float *xyz, const float *k0, uint32_t Nx,
-                                          uint32_t Ny, uint32_t Nz, uint32_t C,
-                                          uint32_t pos_freqs, const float *view,
-                                          uint32_t view_dim, const float *box, float bound,
-                                          const float *const *params, const void *grad_albedo,
-                                          int grad_albedo_dtype, uint32_t M, void *scratch,
-                                          float *const *grads, int accumulate,
-                                          dfhip_stream_t stream) {
-    const char *name = "voxel_field_backward";
-    Geom G;
+// Device count: the images of every chunk of the capacity (616 rows x 2 bytes
+// per padded sample), then kSplits partial images per chunk.
+static Scratch scratch_layout_dev(uint32_t cap, uint32_t dim0) {
+    Scratch s;
+    size_t o = 0;
+    s.rows = o, o += (size_t)kRows * ceil_div((size_t)cap, (size_t)32) * 32 * sizeof(half_t);
+    s.partial = o, o += ceil_div((size_t)ceil_div(cap, kChunk) * kSplits *
+                                     t_offset(kTensors, dim0) * sizeof(float), (size_t)16) * 16;
+    s.total = o ? o : 16;
+    return s;
+}
+
+extern "C" uint64_t dfhip_voxel_field_backward_dev_scratch(uint32_t cap, uint32_t dim0) {
+    if (dim0 > (uint32_t)kInPad) dim0 = kInPad;
+    return (uint64_t)scratch_layout_dev(cap, dim0).total;
+}
+
+// The checks both backward entries share; fills G, P, Gp.
+static int backward_args(const char *name, uint32_t Nx, uint32_t Ny, uint32_t Nz, uint32_t C,
+                         uint32_t pos_freqs, uint32_t view_dim, const float *box, float bound,
+                         const float *const *params, int grad_albedo_dtype, float *const *grads,
+                         Geom &G, Ptrs &P, GPtrs &Gp) {
     if (!geometry(name, Nx, Ny, Nz, C, pos_freqs, view_dim, box, bound, 0.0f, true, G))
         return DFHIP_EINVAL;
-    Ptrs P;
     if (!gather(name, params, P)) return DFHIP_EINVAL;
-    GPtrs Gp;
     if (!grads) {
         set_error("%s: null gradient list", name);
         return DFHIP_EINVAL;
@@ -404,6 +609,24 @@ extern "C" int dfhip_voxel_field_backward(const float *xyz, const float *k0, uin
         set_error("%s: grad_albedo dtype must be f16 or f32", name);
         return DFHIP_EDTYPE;
     }
+    return DFHIP_OK;
+}
+
+extern "C" int dfhip_voxel_field_backward(const float *xyz, const float *k0, uint32_t Nx,
+                                          uint32_t Ny, uint32_t Nz, uint32_t C,
+                                          uint32_t pos_freqs, const float *view,
+                                          uint32_t view_dim, const float *box, float bound,
+                                          const float *const *params, const void *grad_albedo,
+                                          int grad_albedo_dtype, uint32_t M, void *scratch,
+                                          float *const *grads, int accumulate,
+                                          dfhip_stream_t stream) {
+    const char *name = "voxel_field_backward";
+    Geom G;
+    Ptrs P;
+    GPtrs Gp;
+    if (int rc = backward_args(name, Nx, Ny, Nz, C, pos_freqs, view_dim, box, bound, params,
+                               grad_albedo_dtype, grads, G, P, Gp))
+        return rc;
     hipStream_t s = as_stream(stream);
     if (M == 0) {
         if (!accumulate)
@@ -433,13 +656,11 @@ extern "C" int dfhip_voxel_field_backward(const float *xyz, const float *k0, uin
         const void *ga = (const char *)grad_albedo + (size_t)m0 * 3 * ga_size;
         const uint32_t nblk = persistent_blocks(tiles, kBwdWaves);
         if (grad_albedo_dtype == DFHIP_F16)
-            k_voxel_bwd_act<half_t><<<nblk, 64 * kBwdWaves, 0, s>>>(x, k0, view, G, P,
-                                                                (const half_t *)ga, m, tiles, mp,
-                                                                rows);
+            k_voxel_bwd_act<half_t, false><<<nblk, 64 * kBwdWaves, 0, s>>>(
+                x, k0, view, G, P, (const half_t *)ga, m, tiles, mp, rows, nullptr, 1u);
         else
-            k_voxel_bwd_act<float><<<nblk, 64 * kBwdWaves, 0, s>>>(x, k0, view, G, P,
-                                                               (const float *)ga, m, tiles, mp,
-                                                               rows);
+            k_voxel_bwd_act<float, false><<<nblk, 64 * kBwdWaves, 0, s>>>(
+                x, k0, view, G, P, (const float *)ga, m, tiles, mp, rows, nullptr, 1u);
         const uint32_t splits = mp / 32u < kSplits ? mp / 32u : kSplits;
         k_voxel_wgrad<<<dim3(kJobs, splits), 64, 0, s>>>(rows, mp, G.dim0, partial);
         k_voxel_reduce<<<ceil_div(total, 64u), 1024, 0, s>>>(partial, splits, G.dim0, Gp,
@@ -448,11 +669,63 @@ extern "C" int dfhip_voxel_field_backward(const float *xyz, const float *k0, uin
     return check_launch(name);
 }
 
-extern "C" int dfhip_voxel_normal(const float *xyz, const float *density, uint32_t Nx,
-                                  uint32_t Ny, uint32_t Nz, const float *box, float bound,
-                                  float act_shift, float *normal, uint32_t M,
-                                  dfhip_stream_t stream) {
-    const char *name = "voxel_normal";
+extern "C" int dfhip_voxel_field_backward_dev(const float *xyz, const float *k0, uint32_t Nx,
+                                              uint32_t Ny, uint32_t Nz, uint32_t C,
+                                              uint32_t pos_freqs, const float *view,
+                                              uint32_t view_dim, const float *box, float bound,
+                                              const float *const *params,
+                                              const void *grad_albedo, int grad_albedo_dtype,
+                                              uint32_t cap, const int32_t *m_dev, uint32_t align,
+                                              void *scratch, float *const *grads, int accumulate,
+                                              dfhip_stream_t stream) {
+    const char *name = "voxel_field_backward_dev";
+    Geom G;
+    Ptrs P;
+    GPtrs Gp;
+    if (int rc = backward_args(name, Nx, Ny, Nz, C, pos_freqs, view_dim, box, bound, params,
+                               grad_albedo_dtype, grads, G, P, Gp))
+        return rc;
+    if (!device_count(name, cap, m_dev, align)) return DFHIP_EINVAL;
+    if (!scratch || ((uintptr_t)scratch & 15u)) {
+        set_error("%s: scratch must be a 16-byte aligned buffer of "
+                  "dfhip_voxel_field_backward_dev_scratch(cap, dim0) bytes", name);
+        return DFHIP_EINVAL;
+    }
+    if (cap && (!xyz || !k0 || !grad_albedo || (view_dim && !view))) {
+        set_error("%s: null pointer", name);
+        return DFHIP_EINVAL;
+    }
+    hipStream_t s = as_stream(stream);
+    const Scratch L = scratch_layout_dev(cap, G.dim0);
+    half_t *rows = (half_t *)((char *)scratch + L.rows);
+    float *partial = (float *)((char *)scratch + L.partial);
+    const uint32_t total = t_offset(kTensors, G.dim0);
+    if (cap) {
+        // launch shapes of the capacity; the kernels stop at the live chunks
+        const uint32_t tiles = ceil_div(cap, 32u) * 2u;
+        const uint32_t nblk = persistent_blocks(tiles, kBwdWaves);
+        if (grad_albedo_dtype == DFHIP_F16)
+            k_voxel_bwd_act<half_t, true><<<nblk, 64 * kBwdWaves, 0, s>>>(
+                xyz, k0, view, G, P, (const half_t *)grad_albedo, cap, tiles, 0u, rows, m_dev,
+                align);
+        else
+            k_voxel_bwd_act<float, true><<<nblk, 64 * kBwdWaves, 0, s>>>(
+                xyz, k0, view, G, P, (const float *)grad_albedo, cap, tiles, 0u, rows, m_dev,
+                align);
+        const uint32_t first = padded(cap < kChunk ? cap : kChunk);
+        const uint32_t splits = first / 32u < kSplits ? first / 32u : kSplits;
+        k_voxel_wgrad_dev<<<dim3(kJobs, splits), 64, 0, s>>>(rows, cap, m_dev, align, G.dim0,
+                                                             partial);
+    }
+    k_voxel_reduce_dev<<<ceil_div(total, 64u), 1024, 0, s>>>(partial, cap, m_dev, align, G.dim0,
+                                                             Gp, accumulate ? 1 : 0);
+    return check_launch(name);
+}
+
+// m_dev NULL: M rows; else M is the capacity and *m_dev the live count
+static int field_normal(const char *name, const float *xyz, const float *density, uint32_t Nx,
+                        uint32_t Ny, uint32_t Nz, const float *box, float bound, float act_shift,
+                        float *normal, uint32_t M, const int32_t *m_dev, dfhip_stream_t stream) {
     Geom G;
     if (!geometry(name, Nx, Ny, Nz, 0u, 0u, 0u, box, bound, act_shift, false, G))
         return DFHIP_EINVAL;
@@ -461,6 +734,30 @@ extern "C" int dfhip_voxel_normal(const float *xyz, const float *density, uint32
         set_error("%s: null pointer", name);
         return DFHIP_EINVAL;
     }
-    k_voxel_normal<<<ceil_div(M, 256u), 256, 0, as_stream(stream)>>>(xyz, density, G, normal, M);
+    if (m_dev)
+        k_voxel_normal<true><<<ceil_div(M, 256u), 256, 0, as_stream(stream)>>>(xyz, density, G,
+                                                                               normal, M, m_dev);
+    else
+        k_voxel_normal<false><<<ceil_div(M, 256u), 256, 0, as_stream(stream)>>>(xyz, density, G,
+                                                                                normal, M, nullptr);
     return check_launch(name);
+}
+
+extern "C" int dfhip_voxel_normal(const float *xyz, const float *density, uint32_t Nx,
+                                  uint32_t Ny, uint32_t Nz, const float *box, float bound,
+                                  float act_shift, float *normal, uint32_t M,
+                                  dfhip_stream_t stream) {
+    return field_normal("voxel_normal", xyz, density, Nx, Ny, Nz, box, bound, act_shift, normal,
+                        M, nullptr, stream);
+}
+
+extern "C" int dfhip_voxel_normal_dev(const float *xyz, const float *density, uint32_t Nx,
+                                      uint32_t Ny, uint32_t Nz, const float *box, float bound,
+                                      float act_shift, float *normal, uint32_t cap,
+                                      const int32_t *m_dev, uint32_t align,
+                                      dfhip_stream_t stream) {
+    const char *name = "voxel_normal_dev";
+    if (!device_count(name, cap, m_dev, align)) return DFHIP_EINVAL;
+    return field_normal(name, xyz, density, Nx, Ny, Nz, box, bound, act_shift, normal, cap, m_dev,
+                        stream);
 }

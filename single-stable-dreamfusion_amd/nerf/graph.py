@@ -27,15 +27,20 @@ replayed:
   graph replays.
 
 The albedo shading is captured in both forms; the textureless / lambertian
-steps (finite-difference normals, csrc/shade.hip) only as the native step.  RNG draws inside the graph (march noise, background colour, light
-direction, timestep, SDS noise) use torch's graph-safe Philox offsets, so
-every replay draws fresh numbers.
+steps (finite-difference normals, csrc/shade.hip) only as the native step.  The
+DVGO backbone's steps are captured only as its own native step
+(nerf/native_voxel_step.py: the same capture, NativeVoxelStep in the place of
+NativeAlbedoStep; its background network's autograd is recorded in the graph).
+RNG draws inside the graph (march noise, background colour, light direction,
+timestep, SDS noise) use torch's graph-safe Philox offsets, so every replay
+draws fresh numbers.
 """
 import torch
 
 import _dfhip
 from . import field as _field
 from . import native_step as _native
+from . import native_voxel_step as _voxel
 
 
 class GraphedTrainStep:
@@ -45,10 +50,17 @@ class GraphedTrainStep:
         self.H, self.W = data["H"], data["W"]
         # the albedo step as native launches without autograd (nerf/native_step.py)
         self.native = None
-        if (trainer.native_step and allow_native and "pose" in data and "intrinsics" in data
-                and _native.eligible(trainer, shading)):
+        posed = trainer.native_step and allow_native and "pose" in data and "intrinsics" in data
+        if _voxel.serves(trainer.model):
+            # the DVGO backbone: the native voxel step or no graph at all
+            if not (posed and _voxel.eligible(trainer, shading)):
+                raise RuntimeError("the dvgo backbone's step is graphed only as the native "
+                                   "voxel step (nerf/native_voxel_step.py eligible())")
+            self.native = _voxel.NativeVoxelStep(trainer, self.H, self.W, shading, ambient_ratio)
+        elif posed and _native.eligible(trainer, shading):
             self.native = _native.NativeAlbedoStep(trainer, self.H, self.W, shading,
                                                    ambient_ratio)
+        if self.native is not None:
             self.rays_o = self.native.rays_o.view(1, -1, 3)
             self.rays_d = self.native.rays_d.view(1, -1, 3)
         else:
@@ -197,10 +209,18 @@ class GraphedTrainStep:
         backward; leaves every trainable parameter's .grad set (and, with
         optimizer_in_graph, the parameters already updated)."""
         self.graph.replay()
+        self._count_served()
         for launch, _ in self.deferred:
             launch()
         for p, g in self.grads:
             p.grad = g
+
+    def _count_served(self):
+        """The voxel step counts the steps it served on the model
+        (native_step_calls): replays run no Python of the step itself."""
+        served = getattr(self.native, "served", None)
+        if served is not None:
+            served()
 
     def stores_live_count(self):
         """True when the step's last launch (the optimizer's finalize, in the graph)
@@ -220,6 +240,7 @@ class GraphedTrainStep:
             raise RuntimeError("step_timed: only the native step has an eager twin")
         nat.body()
         nat.embedding_backward()
+        self._count_served()
         if self.optimizer_in_graph:
             if nat.dp_world is not None:
                 nat.allreduce_tail()

@@ -33,9 +33,15 @@ NeRFRenderer._infer_fused dispatches on, and `native_render_calls` counts the
 frames so rendered (each also counts once in `native_calls` and, shaded, in
 `native_normal_calls`: the native field served it, in one evaluation where
 the host loop makes one per iteration); `native_infer = False` returns to the
-host loop.  The
-native background head and the native train step do not serve this backbone
-(native_background_layers returns None).
+host loop.
+
+Graph-replayed training (Trainer graph_step) runs this backbone's steps as
+NativeVoxelStep (nerf/native_voxel_step.py: the device-count forms of the
+field kernels, the training shading entry of csrc/voxelstep.hip, bg_net
+through torch inside the graph) where its eligible() holds, and eagerly where
+it does not; `native_step_calls` counts the steps so served.  The native
+background head does not describe bg_net (native_background_layers returns
+None).
 """
 import math
 
@@ -199,6 +205,8 @@ class NeRFNetwork(NeRFRenderer):
         self.native_calls = self.native_normal_calls = self.torch_calls = 0
         # eval frames rendered by the fused persistent launch (csrc/voxelrender.hip)
         self.native_render_calls = 0
+        # train steps served by the native voxel step (nerf/native_voxel_step.py)
+        self.native_step_calls = 0
         if self.bg_radius > 0:
             self.num_layers_bg = num_layers_bg
             self.hidden_dim_bg = hidden_dim_bg

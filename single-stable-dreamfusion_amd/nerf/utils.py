@@ -581,7 +581,8 @@ class Trainer(object):
         self.local_step += 1
         self.global_step += 1
         shading, ambient_ratio = self.pick_shading()
-        native_only = shading != "albedo" or not self.fused_backward
+        native_only = (shading != "albedo" or not self.fused_backward
+                       or self._voxel_backbone())
         if self._graph_eligible(shading) and (not native_only or
                                               ("pose" in data and "intrinsics" in data)):
             return self._graph_iteration(data, shading, ambient_ratio)
@@ -595,10 +596,21 @@ class Trainer(object):
         return loss.detach() if torch.is_tensor(loss) else loss
 
     # ------------------------------------------------------------ graph step
+    def _voxel_backbone(self):
+        """The model is the DVGO backbone, whose steps are graphed only as the
+        native voxel step (nerf/native_voxel_step.py)."""
+        from . import native_voxel_step as _voxel
+        return _voxel.serves(self.model)
+
     def _graph_eligible(self, shading):
         if not (self.graph_step and self.amp and self.model.cuda_ray
                 and hasattr(self.guidance, "sds_grad") and self.device.type == "cuda"):
             return False
+        if self._voxel_backbone():
+            # never the autograd-form capture: the torch path of capacity-sized
+            # samples gathers by boolean masks, which synchronise with the host
+            from . import native_voxel_step as _voxel
+            return self.native_step and _voxel.eligible(self, shading)
         if not self.fused_backward or shading != "albedo" or self.bf16:
             # the two-pass backward and the normal-shaded steps are graphed only
             # as the native step

@@ -62,11 +62,18 @@ def volume(net):
 
 
 def eligible(net, x):
-    if not getattr(net, "fused_field", False):
-        return False
     if not (x.is_cuda and torch.is_autocast_enabled("cuda")):
         return False
     if torch.get_autocast_dtype("cuda") != torch.float16:
+        return False
+    return model_eligible(net, x.device)
+
+
+def model_eligible(net, device):
+    """The model's share of eligible(): what the native kernels need of the
+    network itself, whatever the autocast state of the caller (the native
+    train step, nerf/native_voxel_step.py, runs them under no autocast)."""
+    if not getattr(net, "fused_field", False):
         return False
     m = net.main_net
     if not 1.0 > 1e-2 + m.act_shift:
@@ -78,7 +85,7 @@ def eligible(net, x):
     ps = rgbnet_params(m.rgbnet)
     if [tuple(p.shape) for p in ps] != _voxelfield.shapes(m.dim0):
         return False
-    if not all(p.dtype == torch.float32 and p.device == x.device
+    if not all(p.dtype == torch.float32 and p.device == device
                for p in ps + [m.density, m.k0, m.xyz_min, m.xyz_max]):
         return False
     vol, pow2 = volume(net)
