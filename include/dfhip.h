@@ -196,6 +196,45 @@ int dfhip_march_rays_train_emit_staged(int dtype, const void *rays_d, uint32_t m
                                        int zero_tail, const float *stage,
                                        dfhip_stream_t stream);
 
+/* The march entries above with per-call options, for tests and tools; the
+ * entries above forward to these with (mode 0, guard_ulps 0, stats NULL).
+ * With dt_gamma == 0 a ray whose t range lies in binades where its candidates
+ * are an arithmetic sequence of f32 bit patterns is marched without replaying
+ * the visit chain, after a test that no occupied candidate lies inside an
+ * empty candidate's skip interval; a ray that fails the test is marched again
+ * from its start on the exact path.  Every output is bit-identical either way.
+ *   mode: 0 = as above, 1 = the exact path for every ray.
+ *   guard_ulps: added to the bit pattern of every skip target in that test
+ *     (0 in the product; a large value forces restarts, results unchanged).
+ *   stats: NULL, or two device ints: stats[0] += rays marched again on the
+ *     exact path, stats[1] += rays finished on the chain-free path (rays that
+ *     never started on it count in neither).
+ * dfhip_march_rays_train_count_opts: stage NULL = dfhip_march_rays_train_count,
+ * else dfhip_march_rays_train_count_staged. */
+int dfhip_march_rays_train_count_opts(int dtype, const void *rays_o, const void *rays_d,
+                                      const uint8_t *grid, float bound, float dt_gamma,
+                                      uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H,
+                                      const void *nears, const void *fars, int32_t *rays,
+                                      int32_t *counter, const void *noises,
+                                      int32_t *block_sums, float *stage, uint32_t mode,
+                                      uint32_t guard_ulps, int32_t *stats,
+                                      dfhip_stream_t stream);
+int dfhip_march_rays_train_count_staged_quads_opts(
+    int dtype, const void *rays_o, const void *rays_d, const uint8_t *grid, float bound,
+    float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, const void *nears,
+    const void *fars, int32_t *rays, int32_t *counter, const void *noises, int32_t *block_sums,
+    float *stage, int elem, const float *embeddings, const int32_t *offsets, uint32_t L,
+    float S, uint32_t Hb, uint32_t gridtype, int align_corners, uint32_t rows, void *table,
+    void *quads, uint32_t mode, uint32_t guard_ulps, int32_t *stats, dfhip_stream_t stream);
+int dfhip_march_rays_train_emit_opts(int dtype, const void *rays_o, const void *rays_d,
+                                     const uint8_t *grid, float bound, float dt_gamma,
+                                     uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H,
+                                     uint32_t M, const void *nears, const void *fars,
+                                     void *xyzs, void *dirs, void *deltas, int32_t *rays,
+                                     const void *noises, const int32_t *block_sums,
+                                     int zero_tail, uint32_t mode, uint32_t guard_ulps,
+                                     int32_t *stats, dfhip_stream_t stream);
+
 /* raymarching.cu:580 composite_rays_train_forward(sigmas, rgbs, deltas, rays,
  *   M, N, T_thresh, weights_sum, depth, image) */
 int dfhip_composite_rays_train_forward(int dtype, const void *sigmas,

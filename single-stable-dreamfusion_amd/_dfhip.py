@@ -44,6 +44,17 @@ _SIGS = {
                                     _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "dfhip_march_rays_train_count_staged": [_i32, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32,
                                             _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dfhip_march_rays_train_count_opts": [_i32, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32,
+                                          _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
+                                          _vp, _vp],
+    "dfhip_march_rays_train_emit_opts": [_i32, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32, _u32,
+                                         _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                         _u32, _u32, _vp, _vp],
+    "dfhip_march_rays_train_count_staged_quads_opts": [_i32, _vp, _vp, _vp, _f32, _f32, _u32,
+                                                       _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
+                                                       _vp, _vp, _i32, _vp, _vp, _u32, _f32, _u32,
+                                                       _u32, _i32, _u32, _vp, _vp, _u32, _u32,
+                                                       _vp, _vp],
     "dfhip_march_rays_train_emit_staged": [_i32, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
                                            _i32, _vp, _vp],
     "dfhip_composite_rays_train_forward": [_i32, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp,

@@ -67,19 +67,48 @@ def march_rays_train_scratch_ints(N):
     return int(_d.load().dfhip_march_rays_train_scratch_ints(N))
 
 
+def _march_opts(mode, guard_ulps, stats):
+    """The trailing (mode, guard_ulps, stats) of the _opts march entries, or
+    None when all three are the defaults (the plain entry is called then)."""
+    if mode == 0 and guard_ulps == 0 and stats is None:
+        return None
+    if mode not in (0, 1) or not 0 <= guard_ulps < 2 ** 32:
+        raise RuntimeError("mode must be 0 or 1 and guard_ulps a uint32")
+    if stats is not None:
+        checked(stats, "stats", "int")
+        if stats.numel() < 2:
+            raise RuntimeError("stats must hold two ints (restarted, chain-free)")
+    return int(mode), int(guard_ulps), ptr(stats)
+
+
 def march_rays_train_count(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars,
-                           rays, counter, noises, block_sums):
+                           rays, counter, noises, block_sums, mode=0, guard_ulps=0, stats=None):
+    """mode / guard_ulps / stats: see dfhip_march_rays_train_count_opts (tests
+    and tools; results do not depend on them)."""
     dt = _f(rays_o, "rays_o")
     checked(grid, "grid", "u8")
     checked(block_sums, "block_sums", "int")
+    opts = _march_opts(mode, guard_ulps, stats)
+    if opts is not None:
+        call("dfhip_march_rays_train_count_opts", dt, ptr(rays_o), ptr(rays_d), ptr(grid), bound,
+             dt_gamma, max_steps, N, C, H, ptr(nears), ptr(fars), ptr(rays), ptr(counter),
+             ptr(noises), ptr(block_sums), None, *opts, stream())
+        return
     call("dfhip_march_rays_train_count", dt, ptr(rays_o), ptr(rays_d), ptr(grid), bound, dt_gamma,
          max_steps, N, C, H, ptr(nears), ptr(fars), ptr(rays), ptr(counter), ptr(noises),
          ptr(block_sums), stream())
 
 
 def march_rays_train_emit(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears,
-                          fars, xyzs, dirs, deltas, rays, noises, block_sums, zero_tail):
+                          fars, xyzs, dirs, deltas, rays, noises, block_sums, zero_tail, mode=0,
+                          guard_ulps=0, stats=None):
     dt = _f(rays_o, "rays_o")
+    opts = _march_opts(mode, guard_ulps, stats)
+    if opts is not None:
+        call("dfhip_march_rays_train_emit_opts", dt, ptr(rays_o), ptr(rays_d), ptr(grid), bound,
+             dt_gamma, max_steps, N, C, H, M, ptr(nears), ptr(fars), ptr(xyzs), ptr(dirs),
+             ptr(deltas), ptr(rays), ptr(noises), ptr(block_sums), int(zero_tail), *opts, stream())
+        return
     call("dfhip_march_rays_train_emit", dt, ptr(rays_o), ptr(rays_d), ptr(grid), bound, dt_gamma,
          max_steps, N, C, H, M, ptr(nears), ptr(fars), ptr(xyzs), ptr(dirs), ptr(deltas),
          ptr(rays), ptr(noises), ptr(block_sums), int(zero_tail), stream())
@@ -90,7 +119,8 @@ def march_rays_train_stage_floats(N, max_steps):
 
 
 def march_rays_train_count_staged(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears,
-                                  fars, rays, counter, noises, block_sums, stage):
+                                  fars, rays, counter, noises, block_sums, stage, mode=0,
+                                  guard_ulps=0, stats=None):
     """march_rays_train_count that also keeps every sample in `stage` (f32,
     march_rays_train_stage_floats(N, max_steps) floats)."""
     dt = _f(rays_o, "rays_o")
@@ -100,6 +130,12 @@ def march_rays_train_count_staged(rays_o, rays_d, grid, bound, dt_gamma, max_ste
     if stage.dtype != torch.float32 or stage.numel() < march_rays_train_stage_floats(N, max_steps):
         raise RuntimeError("stage must be float32 with march_rays_train_stage_floats(N, max_steps) "
                            "elements")
+    opts = _march_opts(mode, guard_ulps, stats)
+    if opts is not None:
+        call("dfhip_march_rays_train_count_opts", dt, ptr(rays_o), ptr(rays_d), ptr(grid), bound,
+             dt_gamma, max_steps, N, C, H, ptr(nears), ptr(fars), ptr(rays), ptr(counter),
+             ptr(noises), ptr(block_sums), ptr(stage), *opts, stream())
+        return
     call("dfhip_march_rays_train_count_staged", dt, ptr(rays_o), ptr(rays_d), ptr(grid), bound,
          dt_gamma, max_steps, N, C, H, ptr(nears), ptr(fars), ptr(rays), ptr(counter),
          ptr(noises), ptr(block_sums), ptr(stage), stream())
@@ -108,7 +144,7 @@ def march_rays_train_count_staged(rays_o, rays_d, grid, bound, dt_gamma, max_ste
 def march_rays_train_count_staged_quads(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H,
                                         nears, fars, rays, counter, noises, block_sums, stage,
                                         embeddings, offsets, S, Hb, gridtype, align_corners,
-                                        table, quads):
+                                        table, quads, mode=0, guard_ulps=0, stats=None):
     """march_rays_train_count_staged with _fieldmlp.grid_quads's work (the
     table copy and corner quads of `embeddings`) done by extra workgroups of
     the same launch.  f32 rays; same outputs as the two calls."""
@@ -130,11 +166,13 @@ def march_rays_train_count_staged_quads(rays_o, rays_d, grid, bound, dt_gamma, m
     if tuple(quads.shape) != (rows, 4):
         raise RuntimeError("quads must be a [rows, 4] int32 tensor")
     elem = _d.BF16 if table.dtype == torch.bfloat16 else _d.F16
-    call("dfhip_march_rays_train_count_staged_quads", dt, ptr(rays_o), ptr(rays_d), ptr(grid),
+    opts = _march_opts(mode, guard_ulps, stats)
+    name = "dfhip_march_rays_train_count_staged_quads" + ("" if opts is None else "_opts")
+    call(name, dt, ptr(rays_o), ptr(rays_d), ptr(grid),
          bound, dt_gamma, max_steps, N, C, H, ptr(nears), ptr(fars), ptr(rays), ptr(counter),
          ptr(noises), ptr(block_sums), ptr(stage), elem, ptr(embeddings), ptr(offsets),
          offsets.shape[0] - 1, float(S), int(Hb), int(gridtype), int(bool(align_corners)), rows,
-         ptr(table), ptr(quads), stream())
+         ptr(table), ptr(quads), *(opts or ()), stream())
 
 
 def march_rays_train_emit_staged(rays_d, max_steps, N, M, xyzs, dirs, deltas, rays, block_sums,

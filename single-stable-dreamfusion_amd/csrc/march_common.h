@@ -445,10 +445,10 @@ __device__ __forceinline__ uint64_t lanes_below(int j) {
 }
 __device__ __forceinline__ int top_lane(uint64_t m) { return 63 - __clzll((long long)m); }
 
-// March one ray with the whole wave (every lane passes the same ray; call from
-// wave-uniform control flow).  Calls emit(i, x, y, z, dt, dl) on each lane
-// holding the ray's i-th occupied sample (i < limit) and returns the sample
-// count: the serial march()'s samples and return value, bit for bit.
+// The exact path of march_wave (below): every setting, every window.  Calls
+// emit(i, x, y, z, dt, dl) on each lane holding the ray's i-th occupied sample
+// (i < limit) and returns the sample count: the serial march()'s samples and
+// return value, bit for bit.
 //
 // Per window each lane j gets its successor in the reference's visit order:
 // j+1 if occupied, else the first lane with t >= tt_j (64: beyond the
@@ -456,9 +456,9 @@ __device__ __forceinline__ int top_lane(uint64_t m) { return 63 - __clzll((long 
 // lane, found with binary lifting (lane m computes the m-th chain node in six
 // shuffle rounds) instead of a serial walk over the skips.
 template <typename Emit>
-__device__ __forceinline__ uint32_t march_wave(const MarchConsts &k, const Ray &r,
-                                               const uint8_t *__restrict__ grid, float t0,
-                                               float far, uint32_t limit, Emit emit) {
+__device__ __forceinline__ uint32_t march_wave_exact(const MarchConsts &k, const Ray &r,
+                                                     const uint8_t *__restrict__ grid, float t0,
+                                                     float far, uint32_t limit, Emit emit) {
     __shared__ uint8_t s_vis[1024];   // one 64-lane flag row per wave (<= 16 waves)
     const int lane = (int)(threadIdx.x & 63);
     uint8_t *vis = s_vis + (threadIdx.x & ~63u);
@@ -603,6 +603,202 @@ __device__ __forceinline__ uint32_t march_wave(const MarchConsts &k, const Ray &
         t_base = tl + clampf(tl * k.dt_gamma, k.dt_min, k.dt_max);
     }
     return count;
+}
+
+// ------------------------------------------------------ chain-free wave march
+// With dt_gamma == 0 a skip from an empty candidate j lands on the first
+// candidate with t >= tt_j, and tt_j is the far face of j's own empty cell:
+// the candidates it jumps over lie in that cell too, unless f32 rounding at
+// the face puts one just past it.  So the samples of a ray are nearly always
+// "every occupied candidate", which needs no successor, no lifting and no
+// flag row: only the test below, which is per-lane bit arithmetic.
+//
+// Skip interval of an empty candidate j: the candidates after j with
+// t < tt_j.  CONFLICT: an occupied candidate inside some empty candidate's
+// skip interval.
+//
+// Lemma.  If a ray has no conflict, its visit chain (march_wave_exact) takes
+// every occupied candidate, whichever empty candidates it passes through.
+// Proof.  The chain starts at candidate 0; let o be an occupied candidate not
+// on it and c the last chain node before o (one exists: candidate 0 is on the
+// chain and is not o).  The node after c lies beyond o.  If c is occupied
+// that node is c + 1 <= o, so it is o: contradiction.  So c is empty and the
+// node after it is the first candidate with t >= tt_c; that it lies beyond o
+// means t_o < tt_c, so o is inside c's skip interval: a conflict.  Windows do
+// not matter to the argument: the exact path carries a skip that leaves a
+// window as `pend` and resumes at the first candidate with t >= pend, which
+// is the same successor.  []
+// The samples, their order, the limit cut, dl and last_t then follow from the
+// emitted set exactly as on the exact path.
+//
+// The test looks at every empty candidate, visited or not, so it can only
+// report conflicts the chain would not have met: that costs a restart, never
+// a wrong result.  Inside a window, empty lane j is checked against the first
+// occupied lane above it (t increases with the lane, so that one decides);
+// its t has the bits b0 + lane * inc, an integer compare.  Across windows
+// `pend` holds the largest tt (as bits; positive floats order as integers) of
+// the empty lanes with no occupied lane above them, and no later occupied
+// candidate may lie below it.
+
+// Per-call options of march_wave (tests and tools; the product passes none).
+struct MarchOpts {
+    uint32_t mode;    // 0: chain-free where it applies, 1: the exact path for every ray
+    uint32_t guard;   // ulps added to every skip target in the conflict test
+    int32_t *stats;   // NULL, or {rays restarted on the exact path, rays finished chain-free}
+};
+
+// Largest v of the wave (0 is the identity): DPP scan, the result in lane 63.
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#define DFHIP_MAX_DPP(ctrl, rows) \
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xF, false))
+    DFHIP_MAX_DPP(0x111, 0xF);   // row_shr:1
+    DFHIP_MAX_DPP(0x112, 0xF);   // row_shr:2
+    DFHIP_MAX_DPP(0x114, 0xF);   // row_shr:4
+    DFHIP_MAX_DPP(0x118, 0xF);   // row_shr:8
+    DFHIP_MAX_DPP(0x142, 0xA);   // row_bcast:15 into rows 1 and 3
+    DFHIP_MAX_DPP(0x143, 0xC);   // row_bcast:31 into rows 2 and 3
+#undef DFHIP_MAX_DPP
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// True when every window the ray can evaluate is arithmetic (wave_window_t
+// returns inc != 0): dt_gamma == 0, t0 positive and normal, and dt neither a
+// tie nor out of range in ulps of any binade from t0's to that of far + dt
+// (a window starts below far + dt).  Wave-uniform.
+__device__ __forceinline__ bool ray_all_arith(const MarchConsts &k, float t0, float far) {
+    if (k.dt_gamma != 0.0f) return false;
+    const float dt = clampf(0.0f, k.dt_min, k.dt_max);
+    const uint32_t b0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(t0));
+    const uint32_t b1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(far + dt));
+    if (b0 < 0x00800000u || b0 >= 0x7F800000u || b1 >= 0x7F800000u) return false;
+    for (uint32_t ex = b0 >> 23; ex <= (b1 >> 23); ++ex) {
+        const float D = ldexpf(dt, 150 - (int)ex);
+        if (!(D >= 0.5f && D < 8388608.0f && fabsf(D - rintf(D)) != 0.5f)) return false;
+    }
+    return true;
+}
+
+// One window's candidates, evaluated as march_wave_exact evaluates them (the
+// same f32 operations in the same order).
+struct FastWindow {
+    float tj, x, y, z, tt;
+    uint32_t byte, bit;   // the candidate's bitfield byte (0: no candidate) and its bit
+    uint32_t b0, inc;     // bits(t_base); the bit-pattern step (0: not arithmetic)
+    int L, Lf;            // window length; valid candidates (a lane prefix)
+};
+
+__device__ __forceinline__ FastWindow fast_window(const MarchConsts &k, const Ray &r,
+                                                  const uint8_t *__restrict__ grid,
+                                                  float t_base, float far, int lane) {
+    FastWindow w;
+    float rinc;
+    w.L = __builtin_amdgcn_readfirstlane(wave_window_t(k, t_base, lane, w.tj, w.inc, rinc));
+    w.b0 = __float_as_uint(t_base);
+    const bool valid = lane < w.L && w.tj < far;
+    w.Lf = __popcll(__ballot(valid));
+    const float dt = clampf(w.tj * k.dt_gamma, k.dt_min, k.dt_max);
+    w.x = clampf(fmaf(w.tj, r.dx, r.ox), -k.bound, k.bound);
+    w.y = clampf(fmaf(w.tj, r.dy, r.oy), -k.bound, k.bound);
+    w.z = clampf(fmaf(w.tj, r.dz, r.oz), -k.bound, k.bound);
+    const Mip mp = mip_of(k, w.x, w.y, w.z, dt);
+    const int nx = cell_of(k, w.x, mp.rbound);
+    const int ny = cell_of(k, w.y, mp.rbound);
+    const int nz = cell_of(k, w.z, mp.rbound);
+    const uint32_t idx = grid_index(k, mp.level, nx, ny, nz);
+    w.byte = 0;
+    if (valid) w.byte = grid[idx >> 3];
+    w.bit = idx & 7u;
+    const float tx = face_dist(k, nx, r.dx, r.rdx, w.x, mp.bound);
+    const float ty = face_dist(k, ny, r.dy, r.rdy, w.y, mp.bound);
+    const float tz = face_dist(k, nz, r.dz, r.rdz, w.z, mp.bound);
+    w.tt = w.tj + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
+    return w;
+}
+
+// The chain-free march of one ray (see above).  Returns false on a conflict,
+// or at a window that is not arithmetic: the caller then marches the ray again
+// on the exact path, which rewrites whatever emit() stored here.  Else true
+// with the sample count, after the emit() calls march_wave_exact would make.
+template <typename Emit>
+__device__ __forceinline__ bool march_wave_fast(const MarchConsts &k, const Ray &r,
+                                                const uint8_t *__restrict__ grid, float t0,
+                                                float far, uint32_t limit, uint32_t guard,
+                                                Emit emit, uint32_t &count_out) {
+    const int lane = (int)(threadIdx.x & 63);
+    const float dt = clampf(0.0f, k.dt_min, k.dt_max);   // dt_gamma == 0
+    uint32_t count = 0;
+    float last_t = t0;    // t after the previous sample (deltas[1])
+    uint32_t pend = 0;    // bits of the largest skip target still open
+    float t_base = t0;    // candidate 0 of the window
+    // Windows depend on each other through scalars only, but evaluating the
+    // next one (its bitfield load in flight) before this one's byte is looked
+    // at measured 2 us slower (DESIGN.md "Round 11"), so one at a time.
+    for (;;) {
+        const FastWindow w = fast_window(k, r, grid, t_base, far, lane);
+        if (__builtin_amdgcn_readfirstlane((int)w.inc) == 0) return false;
+
+        const bool occ = ((w.byte >> w.bit) & 1u) != 0;
+        const uint64_t omask = __ballot(occ);
+        const bool empty = lane < w.Lf && !occ;
+        const uint32_t bt = __float_as_uint(w.tt);
+        const uint32_t g = bt + min(guard, ~bt);   // saturating
+        const uint64_t above = omask & ~lanes_below(lane + 1);
+        const uint32_t o = above ? (uint32_t)__ffsll((long long)above) - 1u : 0u;
+        const bool bad = occ ? __float_as_uint(w.tj) < pend
+                             : (empty && above != 0 && w.b0 + __umul24(o, w.inc) < g);
+        if (__ballot(bad) != 0) return false;
+        pend = max(pend, wave_max_u32(empty && above == 0 ? g : 0u));
+
+        bool done = w.Lf < w.L;
+        uint64_t E = omask;   // emitted, in lane order
+        const uint32_t room = limit - count;
+        if ((uint32_t)__popcll(E) >= room) {
+            for (uint32_t i = (uint32_t)__popcll(E); i > room; --i) E &= ~(1ull << top_lane(E));
+            done = true;
+        }
+        if (E) {
+            const float tn = w.tj + dt;   // t after taking this sample
+            const uint64_t below = E & lanes_below(lane);
+            const int prev = below ? top_lane(below) : lane;
+            const float tprev = __shfl(tn, prev, 64);
+            if ((E >> lane) & 1ull) {
+                emit(count + (uint32_t)__popcll(below), w.x, w.y, w.z, dt,
+                     tn - (below ? tprev : last_t));
+            }
+            last_t = lane_f(tn, top_lane(E));
+            count += (uint32_t)__popcll(E);
+        }
+        if (done) break;
+        // candidate L = candidate L-1 plus one reference step
+        t_base = lane_f(w.tj, w.L - 1) + dt;
+    }
+    count_out = count;
+    return true;
+}
+
+// March one ray with the whole wave (every lane passes the same ray; call from
+// wave-uniform control flow).  Calls emit(i, x, y, z, dt, dl) on each lane
+// holding the ray's i-th occupied sample (i < limit) and returns the sample
+// count: the serial march()'s samples and return value, bit for bit.  A ray
+// whose windows are all arithmetic is marched chain-free first; on a conflict
+// its stores are waited for and the whole ray is marched again on the exact
+// path (not resumed: the exact path's `pend` is not known mid-ray), so emit()
+// may be called twice for a sample index, the second call with the final
+// values.
+template <typename Emit>
+__device__ __forceinline__ uint32_t march_wave(const MarchConsts &k, const Ray &r,
+                                               const uint8_t *__restrict__ grid, float t0,
+                                               float far, uint32_t limit, Emit emit,
+                                               const MarchOpts &opt = MarchOpts{0u, 0u, nullptr}) {
+    if (limit == 0 || !(t0 < far)) return 0;
+    if (opt.mode == 0u && ray_all_arith(k, t0, far)) {
+        uint32_t count = 0;
+        const bool ok = march_wave_fast(k, r, grid, t0, far, limit, opt.guard, emit, count);
+        if (opt.stats && (threadIdx.x & 63) == 0) atomicAdd(opt.stats + (ok ? 1 : 0), 1);
+        if (ok) return count;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    return march_wave_exact(k, r, grid, t0, far, limit, emit);
 }
 }  // namespace rm
 }  // namespace dfhip

@@ -11,7 +11,10 @@
 //  * march_rays_train marches one ray per wave64: 64 consecutive candidate
 //    steps are tested at once and the reference's visit order is replayed on
 //    the wave's ballots (march_wave, march_common.h), so a ray costs a few
-//    bitfield round trips instead of one per step.  It is deterministic: a
+//    bitfield round trips instead of one per step.  On the default setting
+//    (dt_gamma == 0) the replay is not needed: every occupied candidate is a
+//    sample unless a per-lane test finds a rounding conflict, and then the
+//    ray is marched again with the replay.  It is deterministic: a
 //    count pass (block totals, integer atomics only for the API counter), then
 //    an emit pass that derives each ray's offset from the block totals.
 //    Samples land in ray order, contiguous per ray, so compositing and the
@@ -131,7 +134,8 @@ __global__ __launch_bounds__(256) void k_packbits_f32v(const float *__restrict__
 // ------------------------------------------------------------------ training march
 
 // Rays per workgroup of the train marcher: one wave per ray, 16 waves (8:
-// count 61.7 -> 57.0 us per C2 step, emit 14.2 -> 14.8; tools/ab_march.sh).  The
+// count 61.7 -> 57.0 us per C2 step, emit 14.2 -> 14.8; tools/ab_march.sh; with
+// the chain-free march 16: 43.6 us, 8: 60.7, 4: 107.6, DESIGN.md "Round 11").  The
 // count pass leaves one total per workgroup in block_sums; the emit pass
 // derives a ray's offset from the preceding totals plus the block's counts.
 #ifndef DFHIP_MARCH_RPB
@@ -153,7 +157,7 @@ __device__ __forceinline__ void march_count_block(
     const uint8_t *__restrict__ grid, const MarchConsts &k, uint32_t max_steps, uint32_t N,
     const scalar_t *__restrict__ nears, const scalar_t *__restrict__ fars,
     int32_t *rays, int32_t *counter, const scalar_t *__restrict__ noises,
-    int32_t *block_sums, float *__restrict__ stage) {
+    int32_t *block_sums, float *__restrict__ stage, const MarchOpts &opt) {
     __shared__ int s_cnt[kMarchRaysPerBlock];
     const uint32_t w = threadIdx.x >> 6;
     const uint32_t n = blockIdx.x * kMarchRaysPerBlock + w;
@@ -170,10 +174,10 @@ __device__ __forceinline__ void march_count_block(
                                       float *row = st + (size_t)i * kStageFloats;
                                       row[0] = x; row[1] = y; row[2] = z;
                                       row[3] = dt; row[4] = dl;
-                                  });
+                                  }, opt);
         } else {
             cnt = (int)march_wave(k, r, grid, t0, far, max_steps,
-                                  [](uint32_t, float, float, float, float, float) {});
+                                  [](uint32_t, float, float, float, float, float) {}, opt);
         }
         if ((threadIdx.x & 63) == 0) {
             rays[3 * n + 0] = (int32_t)n;
@@ -198,9 +202,9 @@ __global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_count(
     const uint8_t *__restrict__ grid, MarchConsts k, uint32_t max_steps, uint32_t N,
     const scalar_t *__restrict__ nears, const scalar_t *__restrict__ fars,
     int32_t *rays, int32_t *counter, const scalar_t *__restrict__ noises,
-    int32_t *block_sums, float *__restrict__ stage = nullptr) {
+    int32_t *block_sums, float *__restrict__ stage, MarchOpts opt) {
     march_count_block<scalar_t, STAGE>(rays_o, rays_d, grid, k, max_steps, N, nears, fars, rays,
-                                       counter, noises, block_sums, stage);
+                                       counter, noises, block_sums, stage, opt);
 }
 
 // The staged count pass with a second role: the workgroups past the march's
@@ -228,7 +232,8 @@ __global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_count_q
     const uint8_t *__restrict__ grid, MarchConsts k, uint32_t max_steps, uint32_t N,
     const scalar_t *__restrict__ nears, const scalar_t *__restrict__ fars,
     int32_t *rays, int32_t *counter, const scalar_t *__restrict__ noises,
-    int32_t *block_sums, float *__restrict__ stage, uint32_t march_blocks, QuadRider q) {
+    int32_t *block_sums, float *__restrict__ stage, uint32_t march_blocks, QuadRider q,
+    MarchOpts opt) {
     if (blockIdx.x >= march_blocks) {  // workgroup-uniform
         fm::grid_quads_rows<E>(q.emb, q.offsets, q.lv, q.gridtype, q.align_corners, q.rows,
                                (blockIdx.x - march_blocks) * blockDim.x + threadIdx.x,
@@ -236,7 +241,7 @@ __global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_count_q
         return;
     }
     march_count_block<scalar_t, true>(rays_o, rays_d, grid, k, max_steps, N, nears, fars, rays,
-                                      counter, noises, block_sums, stage);
+                                      counter, noises, block_sums, stage, opt);
 }
 
 template <typename scalar_t>
@@ -266,7 +271,7 @@ __global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_emit(
     const scalar_t *__restrict__ nears, const scalar_t *__restrict__ fars,
     scalar_t *xyzs, scalar_t *dirs, scalar_t *deltas, int32_t *rays,
     const scalar_t *__restrict__ noises, const int32_t *__restrict__ block_sums,
-    int zero_tail, const float *__restrict__ stage = nullptr, uint32_t max_steps = 0) {
+    int zero_tail, const float *__restrict__ stage, uint32_t max_steps, MarchOpts opt) {
     __shared__ int s_part[kMarchRaysPerBlock];
     __shared__ int s_cnt[kMarchRaysPerBlock];
     const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -325,7 +330,7 @@ __global__ __launch_bounds__(64 * kMarchRaysPerBlock) void k_march_train_emit(
                            pd[3 * i + 2] = from_f<scalar_t>(r.dz);
                            pl[2 * i + 0] = from_f<scalar_t>(dt);
                            pl[2 * i + 1] = from_f<scalar_t>(dl);
-                       });
+                       }, opt);
         } else if (zero_tail != 0 && cnt > 0 && off < M) {
             // first ray that does not fit: rows [off, M) stay unwritten -> zero
             // (end clipped by the align limit, like the tail below)
@@ -766,16 +771,45 @@ extern "C" int dfhip_march_rays_train_count(int dtype, const void *rays_o, const
                                             int32_t *rays, int32_t *counter,
                                             const void *noises, int32_t *block_sums,
                                             dfhip_stream_t stream) {
-    if (!march_args_ok("march_rays_train_count", C, H, max_steps)) return DFHIP_EINVAL;
+    return dfhip_march_rays_train_count_opts(dtype, rays_o, rays_d, grid, bound, dt_gamma,
+                                             max_steps, N, C, H, nears, fars, rays, counter,
+                                             noises, block_sums, nullptr, 0, 0, nullptr, stream);
+}
+
+static bool march_mode_ok(const char *what, uint32_t mode) {
+    if (mode > 1u) {
+        set_error("%s: mode must be 0 (default) or 1 (exact path only), got %u", what, mode);
+        return false;
+    }
+    return true;
+}
+
+extern "C" int dfhip_march_rays_train_count_opts(
+    int dtype, const void *rays_o, const void *rays_d, const uint8_t *grid, float bound,
+    float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, const void *nears,
+    const void *fars, int32_t *rays, int32_t *counter, const void *noises, int32_t *block_sums,
+    float *stage, uint32_t mode, uint32_t guard_ulps, int32_t *stats, dfhip_stream_t stream) {
+    const char *name = "march_rays_train_count_opts";
+    if (!march_args_ok(name, C, H, max_steps) || !march_mode_ok(name, mode)) return DFHIP_EINVAL;
     if (N == 0) return DFHIP_OK;
     const MarchConsts k = make_consts(bound, dt_gamma, max_steps, C, H);
-    DFHIP_DISPATCH(dtype, "march_rays_train_count",
-        k_march_train_count<scalar_t><<<ceil_div(N, kMarchRaysPerBlock), 64 * kMarchRaysPerBlock,
-                                        0, as_stream(stream)>>>(
-            (const scalar_t *)rays_o, (const scalar_t *)rays_d, grid, k, max_steps, N,
-            (const scalar_t *)nears, (const scalar_t *)fars, rays, counter,
-            (const scalar_t *)noises, block_sums));
-    return check_launch("march_rays_train_count");
+    const MarchOpts opt{mode, guard_ulps, stats};
+    const uint32_t blocks = ceil_div(N, kMarchRaysPerBlock), threads = 64 * kMarchRaysPerBlock;
+    hipStream_t s = as_stream(stream);
+    if (stage) {
+        DFHIP_DISPATCH(dtype, name,
+            (k_march_train_count<scalar_t, true><<<blocks, threads, 0, s>>>(
+                (const scalar_t *)rays_o, (const scalar_t *)rays_d, grid, k, max_steps, N,
+                (const scalar_t *)nears, (const scalar_t *)fars, rays, counter,
+                (const scalar_t *)noises, block_sums, stage, opt)));
+    } else {
+        DFHIP_DISPATCH(dtype, name,
+            (k_march_train_count<scalar_t, false><<<blocks, threads, 0, s>>>(
+                (const scalar_t *)rays_o, (const scalar_t *)rays_d, grid, k, max_steps, N,
+                (const scalar_t *)nears, (const scalar_t *)fars, rays, counter,
+                (const scalar_t *)noises, block_sums, nullptr, opt)));
+    }
+    return check_launch(name);
 }
 
 extern "C" int dfhip_march_rays_train_emit(int dtype, const void *rays_o, const void *rays_d,
@@ -786,17 +820,31 @@ extern "C" int dfhip_march_rays_train_emit(int dtype, const void *rays_o, const 
                                            void *deltas, int32_t *rays, const void *noises,
                                            const int32_t *block_sums, int zero_tail,
                                            dfhip_stream_t stream) {
-    if (!march_args_ok("march_rays_train_emit", C, H, max_steps)) return DFHIP_EINVAL;
+    return dfhip_march_rays_train_emit_opts(dtype, rays_o, rays_d, grid, bound, dt_gamma,
+                                            max_steps, N, C, H, M, nears, fars, xyzs, dirs,
+                                            deltas, rays, noises, block_sums, zero_tail, 0, 0,
+                                            nullptr, stream);
+}
+
+extern "C" int dfhip_march_rays_train_emit_opts(
+    int dtype, const void *rays_o, const void *rays_d, const uint8_t *grid, float bound,
+    float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
+    const void *nears, const void *fars, void *xyzs, void *dirs, void *deltas, int32_t *rays,
+    const void *noises, const int32_t *block_sums, int zero_tail, uint32_t mode,
+    uint32_t guard_ulps, int32_t *stats, dfhip_stream_t stream) {
+    const char *name = "march_rays_train_emit_opts";
+    if (!march_args_ok(name, C, H, max_steps) || !march_mode_ok(name, mode)) return DFHIP_EINVAL;
     if (N == 0) return DFHIP_OK;
     const MarchConsts k = make_consts(bound, dt_gamma, max_steps, C, H);
-    DFHIP_DISPATCH(dtype, "march_rays_train_emit",
-        k_march_train_emit<scalar_t><<<ceil_div(N, kMarchRaysPerBlock), 64 * kMarchRaysPerBlock,
-                                       0, as_stream(stream)>>>(
+    const MarchOpts opt{mode, guard_ulps, stats};
+    DFHIP_DISPATCH(dtype, name,
+        (k_march_train_emit<scalar_t, false><<<ceil_div(N, kMarchRaysPerBlock),
+                                               64 * kMarchRaysPerBlock, 0, as_stream(stream)>>>(
             (const scalar_t *)rays_o, (const scalar_t *)rays_d, grid, k, N, M,
             (const scalar_t *)nears, (const scalar_t *)fars, (scalar_t *)xyzs,
             (scalar_t *)dirs, (scalar_t *)deltas, rays, (const scalar_t *)noises,
-            block_sums, zero_tail));
-    return check_launch("march_rays_train_emit");
+            block_sums, zero_tail, nullptr, 0u, opt)));
+    return check_launch(name);
 }
 
 extern "C" uint64_t dfhip_march_rays_train_stage_floats(uint32_t N, uint32_t max_steps) {
@@ -814,14 +862,9 @@ extern "C" int dfhip_march_rays_train_count_staged(
         set_error("march_rays_train_count_staged: null stage");
         return DFHIP_EINVAL;
     }
-    const MarchConsts k = make_consts(bound, dt_gamma, max_steps, C, H);
-    DFHIP_DISPATCH(dtype, "march_rays_train_count_staged",
-        (k_march_train_count<scalar_t, true><<<ceil_div(N, kMarchRaysPerBlock),
-                                               64 * kMarchRaysPerBlock, 0, as_stream(stream)>>>(
-            (const scalar_t *)rays_o, (const scalar_t *)rays_d, grid, k, max_steps, N,
-            (const scalar_t *)nears, (const scalar_t *)fars, rays, counter,
-            (const scalar_t *)noises, block_sums, stage)));
-    return check_launch("march_rays_train_count_staged");
+    return dfhip_march_rays_train_count_opts(dtype, rays_o, rays_d, grid, bound, dt_gamma,
+                                             max_steps, N, C, H, nears, fars, rays, counter,
+                                             noises, block_sums, stage, 0, 0, nullptr, stream);
 }
 
 extern "C" int dfhip_march_rays_train_count_staged_quads(
@@ -831,8 +874,21 @@ extern "C" int dfhip_march_rays_train_count_staged_quads(
     float *stage, int elem, const float *embeddings, const int32_t *offsets, uint32_t L,
     float S, uint32_t Hb, uint32_t gridtype, int align_corners, uint32_t rows, void *table,
     void *quads, dfhip_stream_t stream) {
+    return dfhip_march_rays_train_count_staged_quads_opts(
+        dtype, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, rays,
+        counter, noises, block_sums, stage, elem, embeddings, offsets, L, S, Hb, gridtype,
+        align_corners, rows, table, quads, 0, 0, nullptr, stream);
+}
+
+extern "C" int dfhip_march_rays_train_count_staged_quads_opts(
+    int dtype, const void *rays_o, const void *rays_d, const uint8_t *grid, float bound,
+    float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, const void *nears,
+    const void *fars, int32_t *rays, int32_t *counter, const void *noises, int32_t *block_sums,
+    float *stage, int elem, const float *embeddings, const int32_t *offsets, uint32_t L,
+    float S, uint32_t Hb, uint32_t gridtype, int align_corners, uint32_t rows, void *table,
+    void *quads, uint32_t mode, uint32_t guard_ulps, int32_t *stats, dfhip_stream_t stream) {
     const char *name = "march_rays_train_count_staged_quads";
-    if (!march_args_ok(name, C, H, max_steps)) return DFHIP_EINVAL;
+    if (!march_args_ok(name, C, H, max_steps) || !march_mode_ok(name, mode)) return DFHIP_EINVAL;
     if (dtype != DFHIP_F32) {
         set_error("%s: f32 rays only", name);
         return DFHIP_EDTYPE;
@@ -861,12 +917,13 @@ extern "C" int dfhip_march_rays_train_count_staged_quads(
     // one row per rider thread, grid-stride past four workgroups per CU
     const uint32_t want = ceil_div(rows, threads), cap = 4u * device_cus();
     const uint32_t riders = want < cap ? want : cap;
+    const MarchOpts opt{mode, guard_ulps, stats};
     hipStream_t s = as_stream(stream);
 #define DFHIP_COUNT_QUADS(E)                                                                   \
     k_march_train_count_quads<float, E><<<march_blocks + riders, threads, 0, s>>>(            \
         (const float *)rays_o, (const float *)rays_d, grid, k, max_steps, N,                   \
         (const float *)nears, (const float *)fars, rays, counter, (const float *)noises,       \
-        block_sums, stage, march_blocks, q)
+        block_sums, stage, march_blocks, q, opt)
     if (elem == DFHIP_F16) DFHIP_COUNT_QUADS(half_t);
     else if (elem == DFHIP_BF16) DFHIP_COUNT_QUADS(bf16_t);
     else {
@@ -896,7 +953,7 @@ extern "C" int dfhip_march_rays_train_emit_staged(
                                               64 * kMarchRaysPerBlock, 0, as_stream(stream)>>>(
             nullptr, (const scalar_t *)rays_d, nullptr, k, N, M, nullptr, nullptr,
             (scalar_t *)xyzs, (scalar_t *)dirs, (scalar_t *)deltas, rays, nullptr, block_sums,
-            zero_tail, stage, max_steps)));
+            zero_tail, stage, max_steps, MarchOpts{0u, 0u, nullptr})));
     return check_launch("march_rays_train_emit_staged");
 }
 
