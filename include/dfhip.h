@@ -800,6 +800,27 @@ int dfhip_grid_field_backward_check(int elem, const void *enc, const float *xyz,
                                     float *gw1, float *gb1, float *gw2, float *gb2, float *gw3,
                                     float *gb3, int accumulate, float *found_inf,
                                     int defer_sum, dfhip_stream_t stream);
+/* dfhip_grid_field_backward_check that also writes the rows' liveness mask for
+ * the binned embedding backward (dfhip_binned_opts.row_live): row r is LIVE iff
+ * r < *m_dev and grad_sigma[r] or one of the three grad_rgb[r] compares unequal
+ * to zero (-0.0 is zero, a NaN is live), tested on the gradients as passed in.
+ * A dead row's d_enc row is all zero, so the embedding backward may skip it.
+ * row_live: one u16 per 16 rows, i.e. bit r & 31 of the u32 word r >> 5
+ * (little-endian); [ceil(cap / 32)] u32 words.  The call writes the u16 of
+ * every tile of 16 rows below 2 ceil(ceil(*m_dev / 16) / 2), so bits from
+ * *m_dev to the end of the last u32 word holding a live-count row are zero;
+ * words past it keep their contents (the binned backward reads the bits of
+ * rows < *m_dev only).  NULL: no mask, dfhip_grid_field_backward_check. */
+int dfhip_grid_field_backward_check_live(int elem, const void *enc, const float *xyz, float bound,
+                                         const float *w1, const float *b1, const float *w2,
+                                         const float *b2, const float *w3, const float *b3,
+                                         const float *grad_sigma, const void *grad_rgb,
+                                         int grad_rgb_dtype, uint32_t cap, const int32_t *m_dev,
+                                         void *d_enc_lbc, float *mlp_partial, uint32_t mlp_parts,
+                                         float *gw1, float *gb1, float *gw2, float *gb2,
+                                         float *gw3, float *gb3, int accumulate, float *found_inf,
+                                         int defer_sum, uint16_t *row_live,
+                                         dfhip_stream_t stream);
 /* The parameter-gradient sums of a train step in ONE launch, issued after the
  * field backward: the field backward's weight-gradient sum (of a
  * dfhip_grid_field_backward_check call with defer_sum = 1, which then launches
@@ -899,6 +920,17 @@ typedef struct dfhip_binned_opts {
                                    non-finite value into grad_embeddings (with accumulate:
                                    the sum written) stores 1.0f here.  Never cleared by
                                    this call; see dfhip_adam_amp_step_tail */
+    const uint32_t *row_live;   /* NULL = every row is live.  One bit per row of grad_lbc
+                                   (bit r & 31 of word r >> 5), as
+                                   dfhip_grid_field_backward_check_live writes it: a row
+                                   whose bit is 0 has an all-zero gradient row and is not
+                                   filed, so the walk takes fewer entries; the result is
+                                   the same bit for bit, since a zero row adds nothing and
+                                   the walk parts are still dealt out by the unmasked entry
+                                   counts.  Single samples (group 1) only: DFHIP_EINVAL
+                                   with stencil groups.  Read for rows < *m_dev only, by
+                                   the binning: a phase-1 call with a mask must run after
+                                   the field backward that writes it */
 } dfhip_binned_opts;
 /* dfhip_grid_backward_binned_scratch / dfhip_grid_encode_backward_binned_stencil
  * with per-call options (group 1 = single samples, eps ignored; group 7 =

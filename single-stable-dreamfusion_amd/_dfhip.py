@@ -176,6 +176,9 @@ _SIGS = {
     "dfhip_grid_field_backward_check": [_i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _i32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp,
                                         _vp, _vp, _i32, _vp, _i32, _vp],
+    "dfhip_grid_field_backward_check_live": [_i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _i32, _u32, _vp, _vp, _vp, _u32, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp],
     "dfhip_march_rays_train_count_staged_quads": [_i32, _vp, _vp, _vp, _f32, _f32, _u32, _u32,
                                                   _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                   _i32, _vp, _vp, _u32, _f32, _u32, _u32, _i32,

@@ -169,12 +169,14 @@ def grid_field_forward(xyz, bound, table, offsets, S, H, gridtype, align_corners
 def grid_field_backward(enc, xyz, bound, weights, grad_sigma, grad_rgb, d_enc_lbc, mlp_partial,
                         grads, offsets, total_rows, S, H, gridtype, align_corners,
                         grad_embeddings, grid_partial, grid_parts, m_dev=None, accumulate=False,
-                        found_inf=None, defer_sum=False):
+                        found_inf=None, defer_sum=False, row_live=None):
     """accumulate: add into grads (and grad_embeddings) instead of overwriting
     (the second backward of the reference's two-pass step).  found_inf (f32
     [1]): the weight-gradient sum stores 1.0 there when it writes a non-finite
     value; defer_sum: no weight-gradient sum launch (the caller runs
-    param_grad_sums on mlp_partial).  Both need grad_embeddings None."""
+    param_grad_sums on mlp_partial); row_live (int32 [ceil(cap / 32)]): the
+    rows' liveness mask for the binned embedding backward
+    (dfhip_grid_field_backward_check_live).  All need grad_embeddings None."""
     cap = xyz.shape[0]
     for t, n in ((enc, "enc"), (grad_rgb, "grad_rgb"), (d_enc_lbc, "d_enc")):
         checked(t, n)
@@ -187,19 +189,25 @@ def grid_field_backward(enc, xyz, bound, weights, grad_sigma, grad_rgb, d_enc_lb
     if m_dev is not None:
         checked(m_dev, "m_dev", "int")
     gp = _weights(grads)
-    if found_inf is not None or defer_sum:
+    if found_inf is not None or defer_sum or row_live is not None:
         if grad_embeddings is not None:
-            raise RuntimeError("found_inf / defer_sum: grad_embeddings must be None")
+            raise RuntimeError("found_inf / defer_sum / row_live: grad_embeddings must be None")
         if found_inf is not None:
             _f32(found_inf, "found_inf")
         if d_enc_lbc.dtype != enc.dtype:
             raise RuntimeError("d_enc must have enc's dtype")
-        call("dfhip_grid_field_backward_check",
-             _d.BF16 if enc.dtype == torch.bfloat16 else _d.F16, ptr(enc), ptr(xyz),
-             float(bound), *_weights(weights), ptr(grad_sigma), ptr(grad_rgb),
-             _d.dtype_code(grad_rgb, "grad_rgb"), cap, ptr(m_dev), ptr(d_enc_lbc),
-             ptr(mlp_partial), backward_parts(cap) if cap else 1, *gp, int(bool(accumulate)),
-             ptr(found_inf), int(bool(defer_sum)), stream())
+        head = (_d.BF16 if enc.dtype == torch.bfloat16 else _d.F16, ptr(enc), ptr(xyz),
+                float(bound), *_weights(weights), ptr(grad_sigma), ptr(grad_rgb),
+                _d.dtype_code(grad_rgb, "grad_rgb"), cap, ptr(m_dev), ptr(d_enc_lbc),
+                ptr(mlp_partial), backward_parts(cap) if cap else 1, *gp, int(bool(accumulate)),
+                ptr(found_inf), int(bool(defer_sum)))
+        if row_live is not None:
+            checked(row_live, "row_live", "int")
+            if row_live.dtype != torch.int32 or row_live.numel() * 32 < cap:
+                raise RuntimeError("row_live must be int32 [ceil(cap / 32)]")
+            call("dfhip_grid_field_backward_check_live", *head, ptr(row_live), stream())
+        else:
+            call("dfhip_grid_field_backward_check", *head, stream())
         return
     if enc.dtype == torch.bfloat16:
         # bf16 field: the embedding gradient is the binned backward's (bf16 grads)

@@ -302,14 +302,17 @@ __device__ __forceinline__ void load_tile(TileIn<E, rgb_t> &g, uint32_t tile, co
 // when m_dev is given; d_enc is [16, cap, 2].  MLP_ONLY: the plain MLP's
 // backward (k_mlp_fwd): grad_rgb is dh [cap, 4] in E, no heads, and d_enc is
 // the natural [cap, 32] feature gradient (rows [M, cap) written as zeros).
-template <typename E, typename rgb_t, bool PERM, bool MLP_ONLY = false>
+// LIVE: the rows' liveness mask is written (row_live; an instantiation of its
+// own, so the kernel without a mask is the code it was).
+template <typename E, typename rgb_t, bool PERM, bool MLP_ONLY = false, bool LIVE = false>
 __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
     const E *__restrict__ enc, const float *__restrict__ xyz, const float *w1,
     const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
     const float *__restrict__ grad_sigma, const rgb_t *__restrict__ grad_rgb, uint32_t cap,
     const int32_t *__restrict__ m_dev,
     E *__restrict__ d_enc,          // [16, cap, 2] (level-major)
-    float *__restrict__ partial) {  // [gridDim.x, kParams]
+    float *__restrict__ partial,    // [gridDim.x, kParams]
+    uint16_t *__restrict__ row_live = nullptr) {  // [ceil(cap / 16)] liveness bits, or null
     typedef typename Elem<E>::v8 v8;
     typedef typename Elem<E>::v4 v4;
     __shared__ WeightsG<E> W;
@@ -347,6 +350,7 @@ __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
     const uint32_t tiles = ceil_div(M, 16u);
     const uint32_t per_round = gridDim.x * kBwdWaves;
     const uint32_t rounds = ceil_div(tiles, per_round);
+    const uint32_t live_tiles = (tiles + 1u) & ~1u;  // the liveness mask's tiles: whole u32 words
     // dO^T image columns 4..15 are zero for good (each round writes 0..3)
     st_write4(S, c, kColDO + 4 * h, (E)0.0f, (E)0.0f, (E)0.0f, (E)0.0f);
     // one round: the tile's forward recompute, backward and its share of the
@@ -506,6 +510,22 @@ __global__ __launch_bounds__(64 * kBwdWaves, 2) void k_field_bwd(
     TileIn<E, rgb_t> cur;
     load_tile<E, rgb_t, MLP_ONLY>(cur, tile, enc, xyz, grad_sigma, grad_rgb, M, c, h);
     for (uint32_t round = 0; round < rounds; ++round, tile += per_round) {
+        if constexpr (LIVE && !MLP_ONLY) {
+            // liveness of the tile's 16 rows for the binned embedding backward:
+            // a row is live iff one of its four incoming gradients (as loaded:
+            // lane group h holds output h's) compares unequal to zero (-0.0 is
+            // zero, a NaN is live).  One ballot, the four lane groups folded
+            // on the scalar unit, one u16 store per tile; the tiles up to the
+            // end of the last 32-bit word holding a live-count row are written.
+            // Before the prefetch is issued: the branches' join then waits for
+            // this tile's loads only, which the round needs anyway
+            if (tile < live_tiles) {  // uniform
+                const bool nz = h == 0 ? cur.gs != 0.0f : (float)cur.grgb != 0.0f;
+                const uint64_t bal = __ballot(tile * 16 + c < M && nz);
+                const uint32_t m2 = (uint32_t)bal | (uint32_t)(bal >> 32);
+                if (lane == 0) row_live[tile] = (uint16_t)(m2 | (m2 >> 16));
+            }
+        }
         TileIn<E, rgb_t> nxt;  // the next round's inputs, loaded while this one runs
         load_tile<E, rgb_t, MLP_ONLY>(nxt, tile + per_round, enc, xyz, grad_sigma, grad_rgb, M, c,
                                       h);
@@ -989,7 +1009,8 @@ static int grid_field_backward(
     float *gb1, float *gw2, float *gb2, float *gw3, float *gb3, const int32_t *offsets,
     uint32_t total_rows, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
     float *grad_embeddings, float *grid_partial, uint32_t grid_parts, int accumulate,
-    dfhip_stream_t stream, float *found_inf = nullptr, bool defer_sum = false) {
+    dfhip_stream_t stream, float *found_inf = nullptr, bool defer_sum = false,
+    uint16_t *row_live = nullptr) {
     if (!check_field_grid(name, L)) return DFHIP_EINVAL;
     if (!(bound > 0.0f)) {
         set_error("%s: bound must be > 0", name);
@@ -1013,9 +1034,10 @@ static int grid_field_backward(
         }
         const uint32_t nblk = bwd_blocks(cap);
 #define DFHIP_BWD(E, R)                                                                       \
-    k_field_bwd<E, R, true><<<nblk, 256, 0, s>>>(                                             \
-        (const E *)enc, xyz, w1, b1, w2, b2, w3, b3, grad_sigma, (const R *)grad_rgb, cap,     \
-        m_dev, (E *)d_enc_lbc, mlp_partial)
+    (row_live ? k_field_bwd<E, R, true, false, true> : k_field_bwd<E, R, true, false, false>)  \
+        <<<nblk, 256, 0, s>>>((const E *)enc, xyz, w1, b1, w2, b2, w3, b3, grad_sigma,         \
+                              (const R *)grad_rgb, cap, m_dev, (E *)d_enc_lbc, mlp_partial,    \
+                              row_live)
         if (elem == DFHIP_F16 && grad_rgb_dtype == DFHIP_F32) DFHIP_BWD(half_t, float);
         else if (elem == DFHIP_F16 && grad_rgb_dtype == DFHIP_F16) DFHIP_BWD(half_t, half_t);
         else if (elem == DFHIP_BF16 && grad_rgb_dtype == DFHIP_F32) DFHIP_BWD(bf16_t, float);
@@ -1096,13 +1118,31 @@ extern "C" int dfhip_grid_field_backward_check(
     void *d_enc_lbc, float *mlp_partial, uint32_t mlp_parts, float *gw1, float *gb1, float *gw2,
     float *gb2, float *gw3, float *gb3, int accumulate, float *found_inf, int defer_sum,
     dfhip_stream_t stream) {
+    return dfhip_grid_field_backward_check_live(
+        elem, enc, xyz, bound, w1, b1, w2, b2, w3, b3, grad_sigma, grad_rgb, grad_rgb_dtype, cap,
+        m_dev, d_enc_lbc, mlp_partial, mlp_parts, gw1, gb1, gw2, gb2, gw3, gb3, accumulate,
+        found_inf, defer_sum, nullptr, stream);
+}
+
+extern "C" int dfhip_grid_field_backward_check_live(
+    int elem, const void *enc, const float *xyz, float bound, const float *w1, const float *b1,
+    const float *w2, const float *b2, const float *w3, const float *b3, const float *grad_sigma,
+    const void *grad_rgb, int grad_rgb_dtype, uint32_t cap, const int32_t *m_dev,
+    void *d_enc_lbc, float *mlp_partial, uint32_t mlp_parts, float *gw1, float *gb1, float *gw2,
+    float *gb2, float *gw3, float *gb3, int accumulate, float *found_inf, int defer_sum,
+    uint16_t *row_live, dfhip_stream_t stream) {
+    const char *name = row_live ? "grid_field_backward_check_live" : "grid_field_backward_check";
     if (elem != DFHIP_F16 && elem != DFHIP_BF16) {
-        set_error("grid_field_backward_check: elem must be f16 or bf16");
+        set_error("%s: elem must be f16 or bf16", name);
         return DFHIP_EDTYPE;
     }
-    return grid_field_backward("grid_field_backward_check", elem, enc, xyz, bound, w1, b1, w2, b2,
-                               w3, b3, grad_sigma, grad_rgb, grad_rgb_dtype, cap, m_dev,
-                               d_enc_lbc, mlp_partial, mlp_parts, gw1, gb1, gw2, gb2, gw3, gb3,
-                               nullptr, 0, 16, 0.0f, 0, 0, 0, nullptr, nullptr, 0, accumulate,
-                               stream, found_inf, defer_sum != 0);
+    if (((uintptr_t)row_live & 3u) != 0) {
+        set_error("%s: row_live must be 4-byte aligned (the binning reads u32 words)", name);
+        return DFHIP_EINVAL;
+    }
+    return grid_field_backward(name, elem, enc, xyz, bound, w1, b1, w2, b2, w3, b3, grad_sigma,
+                               grad_rgb, grad_rgb_dtype, cap, m_dev, d_enc_lbc, mlp_partial,
+                               mlp_parts, gw1, gb1, gw2, gb2, gw3, gb3, nullptr, 0, 16, 0.0f, 0, 0,
+                               0, nullptr, nullptr, 0, accumulate, stream, found_inf,
+                               defer_sum != 0, row_live);
 }

@@ -116,6 +116,7 @@ struct Opts {
     bool clean;           // the counts scratch's totals / plan words are zero on entry
     uint64_t *trace;      // debug walk timeline or null
     float *found_inf;     // the sum flags a non-finite value it writes (null: no check)
+    const uint32_t *row_live;  // one bit per gradient row, 0: not filed (null: all live)
 };
 
 static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
@@ -126,6 +127,7 @@ static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
     r.clean = false;
     r.trace = nullptr;
     r.found_inf = nullptr;
+    r.row_live = nullptr;
     if (!o) return true;
     if (o->walk_mode < -1 || o->walk_mode > 1) {
         set_error("binned backward: walk_mode must be -1, 0 or 1 (got %d)",
@@ -144,6 +146,7 @@ static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
     r.clean = o->kept_clean > 0;
     r.trace = o->trace;
     r.found_inf = o->found_inf;
+    r.row_live = o->row_live;
     return true;
 }
 
@@ -309,6 +312,33 @@ __device__ __forceinline__ void append(const uint64_t (&mask)[W], uint32_t b0, u
     }
 }
 
+// Liveness bit of gradient row r (dfhip_binned_opts.row_live; null: every row
+// is live).  A dead row's gradient row is all zero: it is not filed, so the
+// walk never sees it, and the sums are what they were (it added w * 0).
+__device__ __forceinline__ bool row_is_live(const uint32_t *__restrict__ live, uint32_t r) {
+    return !live || ((live[r >> 5] >> (r & 31u)) & 1u) != 0u;
+}
+
+// The walk's plan must not notice a mask: the bin totals that deal out the walk parts
+// (P_b) keep counting the dead rows' entries (`dead`, a second LDS counter per
+// bin: what the unmasked binning would have counted minus what was filed), so
+// every part sums the same tiles as without a mask and the f32 part images —
+// each the f64 sum of the same non-zero products — are the same bit for bit.
+// (Totals of the filed entries alone would cut the bins into other parts, and
+// the result would differ in the f32 rounding of the images.)
+template <uint32_t W>
+__device__ __forceinline__ void count_dead(const uint64_t (&mask)[W], uint32_t b0,
+                                           uint32_t *dead) {
+#pragma unroll
+    for (uint32_t h = 0; h < W; ++h) {
+        uint64_t mk = mask[h];
+        while (mk) {
+            atomicAdd(&dead[b0 + (uint32_t)__builtin_ctzll(mk) + 64u * h], 1u);
+            mk &= mk - 1;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- 1. binning
 template <uint32_t D, bool POW2>
 __global__ __launch_bounds__(1024) void k_bin(const float *__restrict__ inputs,
@@ -316,20 +346,23 @@ __global__ __launch_bounds__(1024) void k_bin(const float *__restrict__ inputs,
                                              BinInfo bi, uint32_t gridtype, int align_corners,
                                              SliceDyn dyn, float inv, uint32_t B,
                                              uint32_t *__restrict__ counts,
-                                             uint16_t *__restrict__ entries) {
+                                             uint16_t *__restrict__ entries,
+                                             const uint32_t *__restrict__ row_live) {
     __shared__ uint32_t cnt[kMaxBins];
+    __shared__ uint32_t dead[kMaxBins];  // entries of dead rows, not filed (see count_dead)
     const bool align = align_corners != 0;
     const uint32_t M = ge::dyn_count(dyn, B);
     const uint32_t T = bi.tile;
     const uint32_t ntiles = ceil_div(M, T);
     const uint32_t nb = bi.nbins;
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) cnt[b] = 0;
+        for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) cnt[b] = dead[b] = 0;
         __syncthreads();
         uint16_t *seg = entries + (size_t)tile * nb * T;
         const uint32_t s_end = min(M, (tile + 1) * T);
         for (uint32_t s = tile * T + threadIdx.x; s < s_end; s += blockDim.x) {
             float x[D];
+            const bool live = row_is_live(row_live, s);
             if (!load_pos<D, POW2>(inputs, dyn, inv, s, x)) continue;
             for (uint32_t l = 0; l < bi.L; ++l) {
                 const LevelCtx c = ge::level_ctx<D>(offsets, lv, l, gridtype, align);
@@ -345,23 +378,25 @@ __global__ __launch_bounds__(1024) void k_bin(const float *__restrict__ inputs,
                     if (mode == 0) slice_mask<D, 0, 1>(lr, cell, bi.shift, ns, mask);
                     else if (mode == 1) slice_mask<D, 1, 1>(lr, cell, bi.shift, ns, mask);
                     else slice_mask<D, 2, 1>(lr, cell, bi.shift, ns, mask);
-                    append<1>(mask, b0, cnt, seg, id, T);
+                    if (live) append<1>(mask, b0, cnt, seg, id, T);
+                    else count_dead<1>(mask, b0, dead);
                 } else {
                     uint64_t mask[2];
                     if (mode == 0) slice_mask<D, 0, 2>(lr, cell, bi.shift, ns, mask);
                     else if (mode == 1) slice_mask<D, 1, 2>(lr, cell, bi.shift, ns, mask);
                     else slice_mask<D, 2, 2>(lr, cell, bi.shift, ns, mask);
-                    append<2>(mask, b0, cnt, seg, id, T);
+                    if (live) append<2>(mask, b0, cnt, seg, id, T);
+                    else count_dead<2>(mask, b0, dead);
                 }
             }
         }
         __syncthreads();
         for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) {
-            const uint32_t v = cnt[b];
+            const uint32_t v = cnt[b], w = v + dead[b];
             counts[(size_t)tile * nb + b] = v;
-            if (v)
+            if (w)
                 atomicAdd(&counts[bi.o_totals + b * kTotSplit + tile % kTotSplit],
-                          v + (uint32_t)DFHIP_SEG_COST);
+                          w + (uint32_t)DFHIP_SEG_COST);
         }
         __syncthreads();
     }
@@ -504,15 +539,22 @@ __global__ __launch_bounds__(1024) void k_bin_fast(const float *__restrict__ inp
                                                   SliceDyn dyn, float inv, uint32_t B,
                                                   uint32_t *__restrict__ counts,
                                                   uint16_t *__restrict__ entries,
+                                                  const uint32_t *__restrict__ row_live,
                                                   Stencil st = Stencil{0.0f, 0.0f}) {
     __shared__ uint32_t cnt[kMaxBins];
+    // single samples: entries of dead rows, counted for the plan's totals but
+    // not filed (see count_dead); stencil groups take no mask
+    __shared__ uint32_t dead[GROUP == 1 ? kMaxBins : 1];
     const float half = align_corners ? 0.0f : 0.5f;
     const uint32_t M = ge::dyn_count(dyn, B);
     const uint32_t T = GROUP == 1 ? bi.tile : kTile;
     const uint32_t ntiles = ceil_div(M, T);
     const uint32_t nb = bi.nbins, shift = bi.shift, smask = (1u << bi.shift) - 1u;
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) cnt[b] = 0;
+        for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) {
+            cnt[b] = 0;
+            if constexpr (GROUP == 1) dead[b] = 0;
+        }
         __syncthreads();
         uint16_t *seg = entries + (size_t)tile * nb * T;
         const uint32_t s_end = min(M, (tile + 1) * T);
@@ -523,10 +565,12 @@ __global__ __launch_bounds__(1024) void k_bin_fast(const float *__restrict__ inp
             // the group's points, mapped to [0, 1]; out-of-range points skip
             float xg[GROUP][3];
             uint32_t in = 0;
+            uint32_t in_all = 0;  // single samples: `in` before the liveness mask
 #pragma unroll
             for (uint32_t a = 0; a < GROUP; ++a) xg[a][0] = xg[a][1] = xg[a][2] = 0.0f;
             if constexpr (GROUP == 1) {
-                if (s < s_end && load_pos<3, POW2>(inputs, dyn, inv, s, xg[0])) in = 1;
+                if (s < s_end && load_pos<3, POW2>(inputs, dyn, inv, s, xg[0])) in_all = 1;
+                in = in_all && row_is_live(row_live, s) ? 1u : 0u;
             } else if (s < s_end) {
                 float xr[3];
 #pragma unroll
@@ -581,11 +625,16 @@ __global__ __launch_bounds__(1024) void k_bin_fast(const float *__restrict__ inp
                 const uint32_t b0 = fl.bin0[l], ns = bi.bin0[l + 1] - b0;
                 if constexpr (GROUP == 1) {
                     uint64_t mask = 0;
-                    if (in) {
+                    if (in_all) {
                         const uint32_t c0 = (uint32_t)floorf(fmaf(xg[0][0], sc, half));
                         const uint32_t c1 = (uint32_t)floorf(fmaf(xg[0][1], sc, half));
                         const uint32_t c2 = (uint32_t)floorf(fmaf(xg[0][2], sc, half));
                         pairs(c0 + c1 * m1 + c2 * m2, mask);
+                    }
+                    if (in_all != in) {  // a dead row: counted for the plan, not filed
+                        const uint64_t one[1] = {mask};
+                        count_dead<1>(one, b0, dead);
+                        mask = 0;
                     }
                     const uint64_t none[6] = {0, 0, 0, 0, 0, 0};
                     if (ns <= DFHIP_BIN_BALLOT_NS)  // uniform
@@ -643,7 +692,8 @@ __global__ __launch_bounds__(1024) void k_bin_fast(const float *__restrict__ inp
             counts[(size_t)tile * nb + b] = v;
             // bin totals weigh a centre entry (seven points) as kCentreCost
             // satellite entries (one point) for the walk's part plan
-            const uint32_t w = (v & 0xFFFFu) * (GROUP > 1 ? kCentreCost : 1u) + (v >> 16);
+            const uint32_t w = (v & 0xFFFFu) * (GROUP > 1 ? kCentreCost : 1u) + (v >> 16) +
+                               (GROUP == 1 ? dead[b] : 0u);
             if (w)
                 atomicAdd(&counts[bi.o_totals + b * kTotSplit + tile % kTotSplit],
                           w + (uint32_t)(GROUP > 1 ? DFHIP_SEG_COST7 : DFHIP_SEG_COST));
@@ -1860,6 +1910,11 @@ static int binned_backward(const char *name, int phase, int grad_dtype, const vo
             return DFHIP_EINVAL;
         }
     }
+    if (group != 1 && op.row_live) {
+        set_error("%s: row_live applies to single samples (group 1); stencil groups take no "
+                  "mask", name);
+        return DFHIP_EINVAL;
+    }
     const gb::Stencil st{eps, bound};
     bi.clear_totals = 1u;  // every call leaves the totals zero (see clear_totals)
     if (phase & 1) {
@@ -1878,28 +1933,30 @@ static int binned_backward(const char *name, int phase, int grad_dtype, const vo
                 if (pow2)
                     gb::k_bin_fast<true, 7><<<gbin, 1024, 0, s>>>(inputs, fl, bi, align_corners,
                                                                    dyn, inv, B, counts,
-                                                                   (uint16_t *)entries, st);
+                                                                   (uint16_t *)entries,
+                                                                   op.row_live, st);
                 else
                     gb::k_bin_fast<false, 7><<<gbin, 1024, 0, s>>>(inputs, fl, bi, align_corners,
                                                                     dyn, inv, B, counts,
-                                                                    (uint16_t *)entries, st);
+                                                                    (uint16_t *)entries,
+                                                                    op.row_live, st);
             } else if (op.fast_bin && fast) {
                 if (pow2)
                     gb::k_bin_fast<true><<<gbin, 1024, 0, s>>>(inputs, fl, bi, align_corners,
                                                                 dyn, inv, B, counts,
-                                                                (uint16_t *)entries);
+                                                                (uint16_t *)entries, op.row_live);
                 else
                     gb::k_bin_fast<false><<<gbin, 1024, 0, s>>>(inputs, fl, bi, align_corners,
                                                                  dyn, inv, B, counts,
-                                                                 (uint16_t *)entries);
+                                                                 (uint16_t *)entries, op.row_live);
             } else if (pow2) {
                 gb::k_bin<3, true><<<gbin, 1024, 0, s>>>(inputs, offsets, lv, bi, gridtype,
                                                          align_corners, dyn, inv, B, counts,
-                                                         (uint16_t *)entries);
+                                                         (uint16_t *)entries, op.row_live);
             } else {
                 gb::k_bin<3, false><<<gbin, 1024, 0, s>>>(inputs, offsets, lv, bi, gridtype,
                                                           align_corners, dyn, inv, B, counts,
-                                                          (uint16_t *)entries);
+                                                          (uint16_t *)entries, op.row_live);
             }
         }
     }

@@ -222,6 +222,14 @@ class NativeAlbedoStep:
         # step's calls skip the clearing launch (BinnedOpts.kept_clean)
         self.bin_scratch = (torch.empty(ne, **i32), torch.zeros(nc, **i32),
                             torch.empty(npf, **f32))
+        # one liveness bit per field row, written by the field backward and
+        # read by the binning (trainer.live_mask): single samples (the albedo
+        # step) and the row-wise bin of a shaded step's 7 M rows.  Stencil
+        # groups take no mask, and the two-pass step's passes would each need
+        # one of their own: they pass none
+        self.live_mask = (bool(getattr(trainer, "live_mask", True)) and trainer.fused_backward
+                          and not self.stencil_bin)
+        self.row_live = torch.zeros((fcap + 31) // 32, **i32)
         sc = trainer.scaler
         if sc.is_enabled() and sc._scale is None:
             sc._lazy_init_scale_growth_tracker(dev)  # what scaler.scale() does on first use
@@ -517,7 +525,8 @@ class NativeAlbedoStep:
                 self.grad_albedo, self.d_enc, self.mlp_partial, [p.grad for p in self.mlp],
                 self.encoder.offsets, self.rows, S, Hb, gridtype, align, None, None,
                 _parts(self.rows, self.C), self.m_field, found_inf=fi,
-                defer_sum=self.merged_sums)
+                defer_sum=self.merged_sums,
+                row_live=self.row_live if self.live_mask else None)
             if self.merged_sums:
                 # one launch: the field's sum, the head's (deferred above) and
                 # the entropy loss, each in its own fixed order
@@ -621,6 +630,8 @@ class NativeAlbedoStep:
         o.kept_clean = 1 if getattr(self.trainer, "kept_clean_scratch", True) else 0
         # the sum reports a non-finite gradient it writes (folded overflow check)
         o.found_inf = ptr(self.found_inf)
+        # rows the field backward marked dead are not filed
+        o.row_live = ptr(self.row_live) if self.live_mask else None
         return o
 
     def time_field(self, reps=5):

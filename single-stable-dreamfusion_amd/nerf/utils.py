@@ -313,6 +313,12 @@ class Trainer(object):
         # native steps: the embedding backward's counts scratch is kept clean
         # by every call (no clearing launch per step; BinnedOpts.kept_clean)
         self.kept_clean_scratch = True
+        # native one-pass steps: the field backward marks the rows whose
+        # incoming gradient is exactly zero (samples past a ray's T < 1e-4
+        # break) and the embedding backward files none of them (same sums:
+        # such a row adds w * 0; BinnedOpts.row_live).  Single samples only:
+        # a shaded step that bins stencil groups runs without the mask
+        self.live_mask = True
         # native steps with the injected SDS gradient: the ray head's forward
         # and backward as one launch (dfhip_ray_head_forward_backward_entropy_loss)
         self.combined_head = True
