@@ -510,6 +510,29 @@ int dfhip_resmlp_field_backward(const float *xyz, const float *const *params,
                                 const float *grad_sigma, const void *grad_albedo,
                                 int grad_albedo_dtype, uint32_t M, float *dx, void *scratch,
                                 float *const *grads, int accumulate, dfhip_stream_t stream);
+/* nerf/renderer.py:496-532 with the vanilla field above as the field: the
+ * vanilla backbone's albedo inference frames in ONE persistent launch
+ * (csrc/resmlprender.hip), the counterpart of dfhip_voxel_render_rays_infer
+ * further down, whose ray, march (bound .. T_thresh), order / chunk_log2 /
+ * tile_w, output and work arguments, their checks, queue layouts and
+ * retirement rules it shares; params is dfhip_resmlp_field_forward's host array
+ * of 19 device pointers, read by the launch itself (no cast, no copy).  Equal
+ * to the loop march_rays -> dfhip_resmlp_field_forward -> composite_rays at
+ * n_step = 1 bit for bit (the same device functions in the same order; albedo
+ * f16, cast to f32 by the compositing).
+ * Out: weights_sum [N], depth [N], image [N,3] f32, every ray written once;
+ *      work: [4] uint32 scratch, words 1, 2 = the composited sample count.
+ * N = 0 clears work and launches nothing.  order NULL: pixel order.  Errors
+ * (DFHIP_EINVAL, before any device work): NULL params or a NULL entry of it,
+ * C = 0 (or > 16), H outside 2..1024, max_steps = 0, chunk_log2 > 16 and a
+ * tile_w that does not tile N with chunk_log2 6 (with an order), NULL work. */
+int dfhip_resmlp_render_rays_infer(uint32_t N, const float *rays_o, const float *rays_d,
+                                   const float *nears, const float *fars, const float *noises,
+                                   float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
+                                   uint32_t H, const uint8_t *grid, float T_thresh,
+                                   const float *const *params, float *weights_sum, float *depth,
+                                   float *image, uint32_t *work, const int32_t *order,
+                                   uint32_t chunk_log2, uint32_t tile_w, dfhip_stream_t stream);
 
 /* ---------------------------------------------------------------- fused voxel field
  * The DVGO backbone of nerf/network_dvgo.py (reference nerf/network.py:245-268

@@ -114,6 +114,9 @@ _SIGS = {
                                   _u32, _u32, _f32, _u32, _u32, _i32, _vp, _vp, _u32, _vp],
     "dfhip_resmlp_field_forward": [_vp, _vp, _vp, _vp, _u32, _vp],
     "dfhip_resmlp_field_backward": [_vp, _vp, _vp, _vp, _i32, _u32, _vp, _vp, _vp, _i32, _vp],
+    "dfhip_resmlp_render_rays_infer": [_u32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32,
+                                       _u32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
+                                       _vp],
     "dfhip_voxel_field_forward": [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp,
                                   _f32, _f32, _vp, _vp, _vp, _u32, _vp],
     "dfhip_voxel_field_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _f32,

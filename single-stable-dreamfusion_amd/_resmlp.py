@@ -58,6 +58,45 @@ def field_forward(xyz, params, sigma, albedo):
          ptr(albedo), M, stream())
 
 
+def render_rays_infer(rays_o, rays_d, nears, fars, noises, bound, dt_gamma, max_steps, C, H,
+                      bitfield, T_thresh, params, weights_sum, depth, image, work, order=None,
+                      chunk_log2=6, tile_w=0):
+    """Albedo inference render of N rays of the vanilla backbone in one launch
+    (csrc/resmlprender.hip, dfhip_resmlp_render_rays_infer).  rays_o / rays_d
+    [N, 3] f32, nears / fars [N] f32, noises [N] f32 or None, bitfield u8 (C
+    cascades of H^3 cells), params: the 19 sigma_net tensors.  Writes
+    weights_sum [N], depth [N], image [N, 3] f32; work: [4] int32 scratch whose
+    words 1, 2 hold the evaluated sample count afterwards.  order / chunk_log2
+    / tile_w: the queue order of _fieldmlp.render_ray_order (None: pixel
+    order)."""
+    n = rays_o.shape[0]
+    for t, what, shp in ((rays_o, "rays_o", (n, 3)), (rays_d, "rays_d", (n, 3)),
+                         (nears, "nears", (n,)), (fars, "fars", (n,)),
+                         (weights_sum, "weights_sum", (n,)), (depth, "depth", (n,)),
+                         (image, "image", (n, 3))):
+        _f32(t, what)
+        if tuple(t.shape) != shp:
+            raise RuntimeError(f"{what} must have shape {shp}, got {tuple(t.shape)}")
+    if noises is not None:
+        _f32(noises, "noises")
+        if tuple(noises.shape) != (n,):
+            raise RuntimeError("noises must be [N]")
+    checked(bitfield, "bitfield", "u8")
+    if bitfield.numel() * 8 < C * H ** 3:
+        raise RuntimeError("bitfield is smaller than C * H^3 / 8 bytes")
+    checked(work, "work", "int")
+    if work.numel() < 4:
+        raise RuntimeError("work must hold 4 int32")
+    if order is not None:
+        checked(order, "order", "int")
+        if tuple(order.shape) != (-(-n // (1 << chunk_log2)),):
+            raise RuntimeError("order must be [ceil(N / 2^chunk_log2)] int32")
+    call("dfhip_resmlp_render_rays_infer", n, ptr(rays_o), ptr(rays_d), ptr(nears), ptr(fars),
+         ptr(noises), float(bound), float(dt_gamma), int(max_steps), int(C), int(H), ptr(bitfield),
+         float(T_thresh), _pointers(params, "param"), ptr(weights_sum), ptr(depth), ptr(image),
+         ptr(work), ptr(order), int(chunk_log2), int(tile_w), stream())
+
+
 def field_backward(xyz, params, grad_sigma, grad_albedo, dx=None, grads=None, accumulate=False,
                    scratch=None):
     """grads: the 19 f32 gradients shaped as params (overwritten, or added

@@ -33,7 +33,7 @@
 #include "resmlp_common.h"
 
 namespace dfhip {
-namespace rm {
+namespace rs {
 
 constexpr int kFwdWaves = 8;
 constexpr uint32_t kChunk = 65536;  // samples per backward chunk
@@ -487,11 +487,11 @@ static void launch_bwd_act(hipStream_t s, uint32_t nblk, const float *xyz, const
             xyz, P, gs, (const float *)ga, m, tiles, state, grows, mp, lnpart, dx);
 }
 
-}  // namespace rm
+}  // namespace rs
 }  // namespace dfhip
 
 using namespace dfhip;
-using namespace dfhip::rm;
+using namespace dfhip::rs;
 
 extern "C" uint32_t dfhip_resmlp_params(void) { return (uint32_t)kParams; }
 

@@ -14,7 +14,7 @@
 #include <math.h>
 
 namespace dfhip {
-namespace rm {
+namespace rs {
 
 using fm::a_nat;
 using fm::a_perm;
@@ -107,13 +107,15 @@ __device__ __forceinline__ half8 b_tiles(const half4 (&v)[kTiles], int s) {
 // Linear's B operand: freqencoder.hip's k_freq_fwd in f32 (layout
 // [x, sin(2^k x), cos(2^k x)], cos as sin(. + pi/2), full-precision sinf),
 // rounded to f16; features 39..63 are the zero padding of K.
-__device__ __forceinline__ half8 enc_operand(const float (&x)[3], int s, int h) {
+// pick(d): coordinate d of the position.
+template <typename Pick>
+__device__ __forceinline__ half8 enc_operand_of(Pick pick, int s, int h) {
     half8 out;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int f = 32 * s + 8 * h + j;
         const int d = f % 3;
-        const float xd = d == 0 ? x[0] : (d == 1 ? x[1] : x[2]);
+        const float xd = pick(d);
         float v = 0.0f;
         if (f < 3) {
             v = xd;
@@ -124,6 +126,21 @@ __device__ __forceinline__ half8 enc_operand(const float (&x)[3], int s, int h) 
         out[j] = (half_t)v;
     }
     return out;
+}
+__device__ __forceinline__ half8 enc_operand(const float (&x)[3], int s, int h) {
+    return enc_operand_of(
+        [&](int d) __attribute__((always_inline)) {
+            return d == 0 ? x[0] : (d == 1 ? x[1] : x[2]);
+        },
+        s, h);
+}
+// The same of a position held in registers (no addressable array: the
+// coordinate picks stay selects where the array form may turn into an indexed
+// stack slot).
+__device__ __forceinline__ half8 enc_operand(float x0, float x1, float x2, int s, int h) {
+    return enc_operand_of(
+        [=](int d) __attribute__((always_inline)) { return d == 0 ? x0 : (d == 1 ? x1 : x2); }, s,
+        h);
 }
 
 // Sum over the 128 neurons of the lane's sample: the lane's own 32 values
@@ -160,96 +177,146 @@ __device__ __forceinline__ float sigmoidf(float z) { return 1.0f / (1.0f + expf(
 // f16 outputs.
 constexpr int kStBlock = 13, kStOut = kBlocks * kStBlock, kStTile = kStOut + 1;
 
-// One 16-sample tile through the field.  hout: f32 of the f16-rounded
-// outputs h[0..3] of the lane's sample (every lane group holds all four).
-// st != nullptr: store the state above (st already points at the tile's
-// vector 0 of this lane).  xrows / arows != nullptr: store the f16 operands
-// of the weight gradients neuron-major ([row][Mp], column `sample`): the
-// encoding (64 rows) and the inputs of layers 1..4 (4 x 128 rows).
-__device__ __forceinline__ void forward_tile(const FwdW &W, const float (&x)[3], int c, int h,
-                                             float (&hout)[4], u32x4 *st, half_t *xrows,
-                                             half_t *arows, size_t Mp, size_t sample) {
-    half8 xb[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        xb[s] = enc_operand(x, s, h);
-        if (xrows)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) xrows[(size_t)(32 * s + 8 * h + j) * Mp + sample] = xb[s][j];
-    }
-    float a[kTiles][4];  // the block's f32 output (the next block's identity)
-    half4 ah[kTiles];    // its f16 rounding (the next Linear's operand)
+// NT 16-sample tiles through the MLP from their encodings xb[n] (the first
+// Linear's B operands, enc_operand), every weight operand and LayerNorm
+// parameter read from LDS once and used for all NT.  Each tile's arithmetic
+// and rounding points are those of NT = 1: MFMA columns are independent.
+// hout[n]: f32 of the f16-rounded outputs h[0..3] of the lane's sample of tile
+// n (every lane group holds all four).  The backward's hooks serve tile 0
+// (their caller runs NT = 1).  st != nullptr: store the state above (st
+// already points at the tile's vector 0 of this lane).  arows != nullptr:
+// store the f16 inputs of layers 1..4 (4 x 128 rows) neuron-major ([row][Mp],
+// column `sample`) for the weight gradients.
+template <int NT>
+__device__ __forceinline__ void mlp_tiles(const FwdW &W, const half8 (&xb)[NT][2], int c, int h,
+                                          float (&hout)[NT][4], u32x4 *st, half_t *arows,
+                                          size_t Mp, size_t sample) {
+    float a[NT][kTiles][4];  // the block's f32 output (the next block's identity)
+    half4 ah[NT][kTiles];    // its f16 rounding (the next Linear's operand)
 #pragma unroll
     for (int l = 0; l < kBlocks; ++l) {
-        float v[kTiles][4];
-        half4 dh[kTiles], sk[kTiles];
+        float v[NT][kTiles][4];
+        half4 dh[NT][kTiles], sk[NT][kTiles];
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) {
-            f4 acc = fm::bias4(W.b[l], 16 * t + 4 * h);
+            // NT > 1: the operands of one accumulator tile at a time (hoisted,
+            // a layer's 128 operand registers spill beside two tiles' state)
+            if constexpr (NT > 1) asm volatile("" ::: "memory");
+            f4 acc[NT], sacc[NT];
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                acc[n] = fm::bias4(W.b[l], 16 * t + 4 * h);
+                sacc[n] = f4{0, 0, 0, 0};
+            }
             if (l == 0) {
-                f4 sacc = f4{0, 0, 0, 0};
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    acc = mfma(a_nat(W.w0d, kLdE, 16 * t + c, 32 * s, h), xb[s], acc);
-                    sacc = mfma(a_nat(W.w0s, kLdE, 16 * t + c, 32 * s, h), xb[s], sacc);
+                    const half8 wd = a_nat(W.w0d, kLdE, 16 * t + c, 32 * s, h);
+                    const half8 ws = a_nat(W.w0s, kLdE, 16 * t + c, 32 * s, h);
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) {
+                        acc[n] = mfma(wd, xb[n][s], acc[n]);
+                        sacc[n] = mfma(ws, xb[n][s], sacc[n]);
+                    }
                 }
-                sk[t] = __builtin_convertvector(sacc, half4);
+#pragma unroll
+                for (int n = 0; n < NT; ++n) sk[n][t] = __builtin_convertvector(sacc[n], half4);
             } else {
 #pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    acc = mfma(a_perm(W.w[l - 1], kLdH, 16 * t + c, s, h), b_tiles(ah, s), acc);
-            }
-            dh[t] = __builtin_convertvector(acc, half4);
+                for (int s = 0; s < 4; ++s) {
+                    const half8 w = a_perm(W.w[l - 1], kLdH, 16 * t + c, s, h);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[t][r] = (float)dh[t][r];
+                    for (int n = 0; n < NT; ++n) acc[n] = mfma(w, b_tiles(ah[n], s), acc[n]);
+                }
+            }
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                dh[n][t] = __builtin_convertvector(acc[n], half4);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[n][t][r] = (float)dh[n][t][r];
+            }
         }
-        float mean, rstd;
-        ln_stats(v, mean, rstd);
+        float mean[NT], rstd[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) ln_stats(v[n], mean[n], rstd[n]);
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) {
-            f4 z;
+            if constexpr (NT > 1) asm volatile("" ::: "memory");
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = 16 * t + 4 * h + r;
-                const float nrm = (v[t][r] - mean) * rstd * W.gamma[l][n] + W.beta[l][n];
-                z[r] = nrm + (l == 0 ? (float)sk[t][r] : a[t][r]);
-                a[t][r] = z[r] * sigmoidf(z[r]);
-            }
-            ah[t] = half4{(half_t)a[t][0], (half_t)a[t][1], (half_t)a[t][2], (half_t)a[t][3]};
-            if (st) {
-                u32x4 zz;
-                __builtin_memcpy(&zz, &z, 16);
-                st[(size_t)(kStBlock * l + 4 + t) * 64] = zz;
-            }
-            if (arows)
+            for (int n = 0; n < NT; ++n) {
+                f4 z;
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    arows[(size_t)(kHid * l + 16 * t + 4 * h + r) * Mp + sample] = ah[t][r];
+                for (int r = 0; r < 4; ++r) {
+                    const int nn = 16 * t + 4 * h + r;
+                    const float nrm =
+                        (v[n][t][r] - mean[n]) * rstd[n] * W.gamma[l][nn] + W.beta[l][nn];
+                    z[r] = nrm + (l == 0 ? (float)sk[n][t][r] : a[n][t][r]);
+                    a[n][t][r] = z[r] * sigmoidf(z[r]);
+                }
+                ah[n][t] = half4{(half_t)a[n][t][0], (half_t)a[n][t][1], (half_t)a[n][t][2],
+                                 (half_t)a[n][t][3]};
+                if (n == 0 && st) {
+                    u32x4 zz;
+                    __builtin_memcpy(&zz, &z, 16);
+                    st[(size_t)(kStBlock * l + 4 + t) * 64] = zz;
+                }
+                if (n == 0 && arows)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        arows[(size_t)(kHid * l + 16 * t + 4 * h + r) * Mp + sample] = ah[n][t][r];
+            }
         }
         if (st) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const half8 two = __builtin_shufflevector(dh[2 * q], dh[2 * q + 1], 0, 1, 2, 3, 4,
-                                                          5, 6, 7);
+                const half8 two = __builtin_shufflevector(dh[0][2 * q], dh[0][2 * q + 1], 0, 1, 2, 3,
+                                                          4, 5, 6, 7);
                 u32x4 dd;
                 __builtin_memcpy(&dd, &two, 16);
                 st[(size_t)(kStBlock * l + q) * 64] = dd;
             }
             st[(size_t)(kStBlock * l + 12) * 64] =
-                u32x4{__float_as_uint(mean), __float_as_uint(rstd), 0u, 0u};
+                u32x4{__float_as_uint(mean[0]), __float_as_uint(rstd[0]), 0u, 0u};
         }
     }
-    f4 o = fm::bias4(W.b4, 4 * h);
+    if constexpr (NT > 1) asm volatile("" ::: "memory");
+    f4 o[NT];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) o = mfma(a_perm(W.w4, kLdH, c, s, h), b_tiles(ah, s), o);
-    const half4 oh = __builtin_convertvector(o, half4);
+    for (int n = 0; n < NT; ++n) o[n] = fm::bias4(W.b4, 4 * h);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) hout[r] = (float)oh[r];
-    if (st) {
-        uint32_t w[2];
-        __builtin_memcpy(w, &oh, 8);
-        st[(size_t)kStOut * 64] = u32x4{w[0], w[1], 0u, 0u};
+    for (int s = 0; s < 4; ++s) {
+        const half8 w = a_perm(W.w4, kLdH, c, s, h);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) o[n] = mfma(w, b_tiles(ah[n], s), o[n]);
     }
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const half4 oh = __builtin_convertvector(o[n], half4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) hout[n][r] = (float)oh[r];
+        if (n == 0 && st) {
+            uint32_t w[2];
+            __builtin_memcpy(w, &oh, 8);
+            st[(size_t)kStOut * 64] = u32x4{w[0], w[1], 0u, 0u};
+        }
+    }
+}
+
+// One 16-sample tile through the field: the encoding of x, then the MLP.
+// xrows != nullptr: store the f16 encoding (64 rows) neuron-major as arows.
+__device__ __forceinline__ void forward_tile(const FwdW &W, const float (&x)[3], int c, int h,
+                                             float (&hout)[4], u32x4 *st, half_t *xrows,
+                                             half_t *arows, size_t Mp, size_t sample) {
+    half8 xb[1][2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        xb[0][s] = enc_operand(x, s, h);
+        if (xrows)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                xrows[(size_t)(32 * s + 8 * h + j) * Mp + sample] = xb[0][s][j];
+    }
+    mlp_tiles<1>(W, xb, c, h, reinterpret_cast<float (&)[1][4]>(hout), st, arows, Mp, sample);
 }
 
 // Sum over the 16 lanes of a row (the 16 samples of a tile), every lane
@@ -269,5 +336,5 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
-}  // namespace rm
+}  // namespace rs
 }  // namespace dfhip

@@ -14,8 +14,16 @@ f32, bf16 or any other width run the torch path below (encoder -> MLP ->
 heads, normal by autograd.grad), and so do shaded training steps, whose
 autograd normal carries a graph (through the Gaussian blob and trunc_exp).
 `native_calls` / `native_normal_calls` / `torch_calls` count which path ran.
-The persistent inference renderer and the native train step do not serve
-this backbone (native_infer_field / native_background_layers return None).
+Albedo eval frames (`--test`, eval_step, test_step, the GUI) render in one
+persistent launch under the same conditions (csrc/resmlprender.hip):
+native_infer_field returns the descriptor NeRFRenderer._infer_fused dispatches
+on, and `native_render_calls` counts the frames (each also counts once in
+`native_calls`, where the host loop makes one call per iteration);
+`native_infer = False` returns to the host loop.  Not covered: the three
+shaded views (their normal is the MLP's input gradient; they keep the host
+loop on the native field and normal), the background MLP (a LayerNorm ResBlock
+net the native ray head does not evaluate: native_background_layers returns
+None) and the native train step.
 The reference's NeRFNetwork_Kailu wrapper of this file is nerf/network_dvgo.py.
 """
 import torch
@@ -77,6 +85,8 @@ class NeRFNetwork(NeRFRenderer):
         self.fused_field = True
         # which path served common_forward / the normal's input gradient
         self.native_calls = self.native_normal_calls = self.torch_calls = 0
+        # eval frames rendered by the fused persistent launch (csrc/resmlprender.hip)
+        self.native_render_calls = 0
         if self.bg_radius > 0:
             self.num_layers_bg = num_layers_bg
             self.hidden_dim_bg = hidden_dim_bg
@@ -148,6 +158,19 @@ class NeRFNetwork(NeRFRenderer):
         else:  # lambertian
             color = albedo * lambertian.unsqueeze(-1)
         return sigma, color, normal
+
+    def native_infer_field(self, shading, x):
+        """The vanilla-field descriptor when the fused inference renderer
+        serves this frame: the albedo shading under the conditions of the
+        native field (fp16 autocast on the GPU, the reference's shape, f32
+        parameters, fused_field); else None, and the host loop runs.  The
+        shaded views need the MLP's input gradient, which the kernel does not
+        hold the weights for."""
+        if shading != "albedo" or not self.native_infer:
+            return None
+        if not _vf.eligible(self, x):
+            return None
+        return _vf.InferField(self)
 
     def density(self, x):
         sigma, albedo = self.common_forward(x)

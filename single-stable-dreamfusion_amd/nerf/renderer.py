@@ -483,7 +483,8 @@ class NeRFRenderer(nn.Module):
         """The field's descriptor when the fused inference renderer can evaluate
         it for `shading`, else None (subclass hook): (encoder, [Linear] * 3)
         for the grid field, an object of kind "voxel" (voxel_field.InferField)
-        for the DVGO backbone."""
+        for the DVGO backbone or "vanilla" (vanilla_field.InferField) for the
+        vanilla one."""
         return None
 
     def invalidate_infer_operands(self):
@@ -504,8 +505,10 @@ class NeRFRenderer(nn.Module):
         finite-difference stencil in the same launch; light_d: [3] device
         tensor, ambient_ratio: the ambient share.  A field descriptor of kind
         "voxel" (nerf/voxel_field.py InferField, the DVGO backbone) takes
-        csrc/voxelrender.hip's launch instead; the queue order, the streams,
-        the noises and the accounting are shared."""
+        csrc/voxelrender.hip's launch instead, one of kind "vanilla"
+        (nerf/vanilla_field.py InferField, albedo only) csrc/resmlprender.hip's;
+        the queue order, the streams, the noises and the accounting are
+        shared."""
         import _fieldmlp
         import numpy as np
         N = rays_o.shape[0]
@@ -515,8 +518,18 @@ class NeRFRenderer(nn.Module):
         image = torch.empty(N, 3, dtype=torch.float32, device=dev)
         work = torch.empty(4, dtype=torch.int32, device=dev)
         noises = torch.rand(N, device=dev) if perturb else None
-        voxel = getattr(field, "kind", None) == "voxel"
-        if voxel:
+        kind = getattr(field, "kind", None)
+        voxel, vanilla = kind == "voxel", kind == "vanilla"
+        if vanilla:
+            # the vanilla backbone (csrc/resmlprender.hip): sigma_net's own f32
+            # parameters, read at launch (no cast, no cache: nothing is stale
+            # after a native optimizer step)
+            import _resmlp
+            weights = field.operands()
+            field.launched(shading)
+            table = quads = None
+            field_bytes = field.field_bytes
+        elif voxel:
             # the DVGO backbone (csrc/voxelrender.hip): the frozen volumes' cached
             # operands and rgbnet's own f32 parameters, read at launch (nothing
             # is cast or copied, so nothing can go stale after a native
@@ -593,7 +606,13 @@ class NeRFRenderer(nn.Module):
         rs = render_stream if render_stream is not None else main
         if rs is not main:  # the render on its own stream (beside a side-stream job)
             rs.wait_stream(main)
-        if voxel:
+        if vanilla:
+            with torch.cuda.stream(rs), _dfhip.timed("resmlp_render_rays_infer", nbytes):
+                _resmlp.render_rays_infer(
+                    *operands, noises, self.bound, dt_gamma, max_steps, self.cascade,
+                    self.grid_size, self.density_bitfield, T_thresh, weights, weights_sum, depth,
+                    image, work, order=order, chunk_log2=cl, tile_w=tile_w)
+        elif voxel:
             # one entry for the four shadings (the shaded ones take light and ratio)
             name = "voxel_render_rays_infer" + ("" if shading == "albedo" else "_shaded")
             with torch.cuda.stream(rs), _dfhip.timed(name, nbytes + (0 if light is None else 12)):
@@ -620,7 +639,8 @@ class NeRFRenderer(nn.Module):
                                                        chunk_log2=cl, tile_w=tile_w)
         if rs is not main:
             main.wait_stream(rs)
-            field_tensors = (vol.density, vol.k0, vol.view) if voxel else (table, quads)
+            field_tensors = ((vol.density, vol.k0, vol.view) if voxel else
+                             () if vanilla else (table, quads))
             for t in (*operands, weights_sum, depth, image, work, order, noises, *field_tensors,
                       light, *weights):
                 if torch.is_tensor(t):

@@ -81,6 +81,31 @@ def vanilla_field(net, x):
     return _VanillaField.apply(x.reshape(-1, 3), *sigma_net_params(net.sigma_net))
 
 
+class InferField:
+    """What NeRFRenderer._infer_fused needs to render this backbone's albedo
+    frames in one persistent launch (csrc/resmlprender.hip): sigma_net's 19
+    f32 parameters themselves, taken when the frame is launched and read by
+    the kernel, so an optimizer step between two frames (torch's or the native
+    Adam, both of which write the parameters in place) is seen by the next
+    frame with no cast and no cache to invalidate."""
+    kind = "vanilla"
+    field_bytes = 4 * 61188  # the parameters, read once per workgroup
+
+    def __init__(self, net):
+        self.net = net
+
+    def launched(self, shading):
+        """Count one fused frame: in native_render_calls, and as ONE native
+        evaluation of the field for the whole frame, where the host loop
+        counts one per iteration."""
+        self.net.native_render_calls += 1
+        self.net.native_calls += 1
+
+    def operands(self):
+        """The 19 sigma_net tensors in state_dict order."""
+        return [p.detach() for p in sigma_net_params(self.net.sigma_net)]
+
+
 def input_gradient(net, x):
     """d sigma.sum() / d x [M, 3] f32 (no graph): the weight-free backward
     with grad_sigma = 1, grad_albedo = 0."""
