@@ -90,9 +90,12 @@ int dfhip_get_rays(const float *pose, float fx, float fy, float cx, float cy,
  *   grid[c] = max(grid[c] * decay, sigma[p]) (torch.maximum, NaN-propagating),
  *   and that new value is added to acc[0], 1 to acc[1] (f64, device; the caller
  *   zeroes acc before the first cascade).  Every cell must be queried once.
- * dfhip_packbits_mean: thresh = min(acc[0] / acc[1], density_thresh) on the
- *   device; bit i of byte n = grid[8n + i] > thresh (grid 16-B aligned f32);
- *   mean_out[0] (optional) = acc[0] / acc[1] as f32. */
+ * dfhip_packbits_mean: mean = acc[0] / acc[1] as f32 (NaN when acc[1] is 0),
+ *   thresh = min(mean, density_thresh) as Python evaluates it on the device:
+ *   density_thresh if density_thresh < mean, else the mean, so a NaN mean is a
+ *   NaN threshold and an all-zero bitfield (renderer.py:606-607); bit i of
+ *   byte n = grid[8n + i] > thresh (strict; grid 16-B aligned f32, else
+ *   DFHIP_EINVAL); mean_out[0] (optional) = mean. */
 int dfhip_density_grid_ema(const float *sigma, const int32_t *indices, uint32_t n,
                            uint32_t cells, float decay, float *grid, double *acc,
                            dfhip_stream_t stream);
@@ -1388,7 +1391,15 @@ int dfhip_shading_backward_bf16(const float *sigma7, const void *albedo7, const 
                                 float lambda_orient, float *grad_sigma7, void *grad_albedo7,
                                 dfhip_stream_t stream);
 /* The step's light direction safe_normalize(rays_o[0] + randn(3))
- * (renderer.py:462-464), drawn from Philox keyed by (seed, step). */
+ * (renderer.py:462-464), drawn from Philox keyed by (seed, step).  The draw
+ * (f32 throughout; rays_o: 3 floats, light: 3 floats, both on the device):
+ *   (x, y, z, w) = Philox4x32-10(counter = (0xFFFFFFFE, step_lo, step_hi, 3),
+ *                                key = (seed_lo, seed_hi)), lo / hi the 32-bit
+ *                  halves of the 64-bit seed and step;
+ *   Box-Muller: ra = sqrt(-2 log(((x >> 8) + 1) 2^-24)), angle a0 = 2 pi (y >> 8) 2^-24,
+ *               rb = sqrt(-2 log(((z >> 8) + 1) 2^-24)), angle a1 = 2 pi (w >> 8) 2^-24;
+ *   randn(3) = (ra cos a0, ra sin a0, rb cos a1);
+ *   light = v / sqrt(max(|v|^2, 1e-20)), v = rays_o + randn(3). */
 int dfhip_shading_light(const float *rays_o, uint64_t seed, uint64_t step, float *light,
                         dfhip_stream_t stream);
 

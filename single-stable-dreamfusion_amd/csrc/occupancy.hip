@@ -110,8 +110,9 @@ __device__ __forceinline__ float mean_thresh(const double *acc, float density_th
     const double cnt = acc[1];
     const float m = cnt > 0.0 ? (float)(acc[0] / cnt) : NAN;
     if (mean) *mean = m;
-    // Python min(mean, thresh): thresh if mean is NaN (comparison false)
-    return (m < density_thresh) ? m : density_thresh;
+    // Python min(mean, thresh): thresh if thresh < mean, else mean, so a NaN
+    // mean (comparison false) stays NaN and no cell passes the strict >
+    return (density_thresh < m) ? density_thresh : m;
 }
 
 __global__ __launch_bounds__(256) void k_packbits_mean(const float *__restrict__ grid,

@@ -30,7 +30,9 @@ __device__ __forceinline__ Normal fd_normal(const float *__restrict__ sigma7, ui
         o.v[a] = -((0.5f * (sp - sn)) / eps);
     }
     o.ss = (o.v[0] * o.v[0] + o.v[1] * o.v[1]) + o.v[2] * o.v[2];
-    o.r = sqrtf(fmaxf(o.ss, 1e-20f));
+    // torch.clamp(min=1e-20) propagates a NaN |v|^2 (fmaxf alone would return
+    // 1e-20): r is NaN, every component of v / r is NaN and the normal is 0
+    o.r = sqrtf(o.ss != o.ss ? o.ss : fmaxf(o.ss, 1e-20f));
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float q = o.v[a] / o.r;
