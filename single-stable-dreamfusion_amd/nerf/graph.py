@@ -35,12 +35,36 @@ RNG draws inside the graph (march noise, background colour, light direction,
 timestep, SDS noise) use torch's graph-safe Philox offsets, so every replay
 draws fresh numbers.
 """
+import contextlib
+import gc
+
 import torch
 
 import _dfhip
 from . import field as _field
 from . import native_step as _native
 from . import native_voxel_step as _voxel
+
+
+@contextlib.contextmanager
+def capture_graph(graph, **kwargs):
+    """torch.cuda.graph with Python's cyclic collector out of the way: dead
+    cycles are collected before the capture begins and the collector stays off
+    until it has ended.  A collection that starts inside a capture finalizes
+    whatever dead cycle it finds there (an earlier Trainer with its graphs,
+    streams and device buffers), i.e. destroys graphs and frees device memory
+    while the stream is capturing; a whole-suite run aborted that way, in the
+    middle of a native step's capture.  torch collected before every capture
+    itself until 2.10 (now only with torch.compiler.config.force_cudagraph_gc)."""
+    gc.collect()
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kwargs):
+            yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 class GraphedTrainStep:
@@ -117,7 +141,7 @@ class GraphedTrainStep:
                 # the dry run's gradient writers may have raised the overflow
                 # flag, and no optimizer tail ran to clear it
                 nat.clear_found_inf()
-            with torch.cuda.graph(self.graph, stream=self.stream):
+            with capture_graph(self.graph, stream=self.stream):
                 self.loss = nat.body()
                 nat.embedding_backward()
                 if self.optimizer_in_graph:
@@ -163,7 +187,7 @@ class GraphedTrainStep:
                 t.optimizer.zero_grad(set_to_none=True)
             model.local_step = step0
             with _field.defer_embedding_backward() as deferred:
-                with torch.cuda.graph(self.graph, stream=self.stream):
+                with capture_graph(self.graph, stream=self.stream):
                     self.loss = self._body(static).detach()
             torch.cuda.current_stream().wait_stream(self.stream)
         finally:
@@ -397,7 +421,7 @@ class BucketedModuleStep:
             for p in self.params:
                 p.grad = None
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self.stream, pool=self.pool):
+            with capture_graph(g, stream=self.stream, pool=self.pool):
                 loss = self._body(rows).detach()
             torch.cuda.current_stream().wait_stream(self.stream)
         finally:
