@@ -513,6 +513,56 @@ int dfhip_resmlp_field_backward(const float *xyz, const float *const *params,
                                 const float *grad_sigma, const void *grad_albedo,
                                 int grad_albedo_dtype, uint32_t M, float *dx, void *scratch,
                                 float *const *grads, int accumulate, dfhip_stream_t stream);
+/* Device-count forms of the two entries above (the vanilla backbone's native
+ * train step, nerf/native_vanilla_step.py): the same arguments with M replaced
+ * by (cap, m_dev, align), the contract of the dfhip_voxel_*_dev entries further
+ * down.  Buffers hold cap rows (cap < 2^31); the live count *m_dev (DEVICE
+ * int32, clamped to [0, cap]) is read by the kernels.  Launch shapes depend on
+ * cap only, no memset is decided on the host and nothing is read back, so the
+ * entries capture into a graph.  align >= 1; the effective row count is
+ * Me = min(cap, align_up(*m_dev, align)): align = 128 is the slice of
+ * march_rays_train, align = 1 the bare count.
+ * Forward: rows [0, *m_dev) carry the host-count entry's bits; rows at or past
+ * the live count are neither read nor written (align is checked and otherwise
+ * unused).
+ * Backward (parameter gradients only, no dx): rows [0, *m_dev) of xyz,
+ * grad_sigma and grad_albedo are read; rows [*m_dev, Me) act as padding rows
+ * (position 0, gradients 0, never read).  The 19 gradients are bit-identical
+ * to dfhip_resmlp_field_backward with M = Me and dx = NULL on buffers whose
+ * rows [*m_dev, Me) hold those zeros: the same 65536-row chunks in order,
+ * min(mp / 32, 64) splits per chunk with the same k-step ranges, the same
+ * fixed-order sums, and per chunk the gradient pass's tile-to-workgroup
+ * assignment of the host-count entry (min(ceil(tiles / 8), CUs, 256)
+ * workgroups, workgroup b's wave w walking tiles 8 b + w, + 8 workgroups, ...;
+ * one LayerNorm-parameter partial per workgroup): a workgroup of the launch
+ * plays workgroup b of every live chunk in turn.  Four launches whatever the
+ * count: the saving forward over the live tiles, the gradient pass over the
+ * live tiles, the weight gradients (a wave takes its split of every live chunk
+ * in turn), one reduction over the chunks in order.  *m_dev = 0 writes zero
+ * gradients from the kernel, or leaves them untouched with accumulate.
+ * Deterministic, no float atomics.
+ * scratch: dfhip_resmlp_field_backward_dev_scratch(cap) bytes, 16-byte
+ * aligned; capacity-sized, the chunks' images no longer share one buffer:
+ *   capp * (3392 + 2464) + ceil(cap / 65536) * (64 * 61188 * 4 + 256 * 4096)
+ * with capp = cap rounded up to 32: per sample 3392 bytes of tile state (53
+ * vectors x 64 lanes x 16 B per 16 rows) and 1232 neuron-major f16 rows (64
+ * encoding + 512 activation + 656 gradient rows x 2 B); per 65536-row chunk
+ * 64 split partials of the 61188 gradients and 256 LayerNorm partials of
+ * 4 x 2 x 128 floats.  cap 131072: 767,557,632 + 33,425,408 = 800,983,040
+ * bytes; 64 x 64 rays at max_steps 512, cap 2097152: 12,280,922,112 +
+ * 534,806,528 = 12,815,728,640 bytes.
+ * Errors before any device work: DFHIP_EINVAL for a NULL params / grads list
+ * or entry, NULL m_dev, align = 0, cap >= 2^31, a NULL or misaligned scratch;
+ * DFHIP_EDTYPE for a grad_albedo_dtype other than F16 / F32. */
+int dfhip_resmlp_field_forward_dev(const float *xyz, const float *const *params, float *sigma,
+                                   void *albedo, uint32_t cap, const int32_t *m_dev,
+                                   uint32_t align, dfhip_stream_t stream);
+uint64_t dfhip_resmlp_field_backward_dev_scratch(uint32_t cap);
+int dfhip_resmlp_field_backward_dev(const float *xyz, const float *const *params,
+                                    const float *grad_sigma, const void *grad_albedo,
+                                    int grad_albedo_dtype, uint32_t cap, const int32_t *m_dev,
+                                    uint32_t align, void *scratch, float *const *grads,
+                                    int accumulate, dfhip_stream_t stream);
 /* nerf/renderer.py:496-532 with the vanilla field above as the field: the
  * vanilla backbone's albedo inference frames in ONE persistent launch
  * (csrc/resmlprender.hip), the counterpart of dfhip_voxel_render_rays_infer
@@ -1156,6 +1206,23 @@ int dfhip_entropy_backward(uint32_t N, const float *ws, const float *grad_loss, 
  * the entropy term and the ray head's gradient of the weights sum, one
  * launch (the native train step, nerf/native_step.py). */
 int dfhip_entropy_backward_accumulate(uint32_t N, const float *ws, const float *grad_loss,
+                                      float lambda, float *grad_ws, dfhip_stream_t stream);
+/* nerf/utils.py opacity regulariser lambda_opacity * (pred_ws ** 2).mean():
+ * loss[0] = f32(lambda * sum_f64(ws_i^2) / N), squares and sum in f64 in
+ * dfhip_entropy_forward's fixed reduction order (one 1024-thread block);
+ * accumulate != 0 adds that f32 value onto loss[0] (an entropy loss already
+ * written).  N = 0 writes (adds) nothing.
+ * Backward, added into grad_ws as the autograd sum of the term and the ray
+ * head's gradient of the weights sum: grad_ws_i += ((grad_loss[0] * lambda) /
+ * N) * (2 * ws_i), every operation an f32 rounding in that order.  This is
+ * autograd's chain: mul's backward grad_loss * lambda, mean's backward / N
+ * (torch multiplies by the f32 reciprocal of N instead, the same bits for the
+ * power-of-two ray counts of square power-of-two images and within one ulp
+ * otherwise), pow's backward g * (2 * ws).  grad_loss: the DEVICE loss scale,
+ * as for the entropy entries. */
+int dfhip_opacity_forward(uint32_t N, const float *ws, float lambda, float *loss, int accumulate,
+                          dfhip_stream_t stream);
+int dfhip_opacity_backward_accumulate(uint32_t N, const float *ws, const float *grad_loss,
                                       float lambda, float *grad_ws, dfhip_stream_t stream);
 
 /* Prologue of the native albedo train step (nerf/native_step.py), one launch:

@@ -114,6 +114,9 @@ _SIGS = {
                                   _u32, _u32, _f32, _u32, _u32, _i32, _vp, _vp, _u32, _vp],
     "dfhip_resmlp_field_forward": [_vp, _vp, _vp, _vp, _u32, _vp],
     "dfhip_resmlp_field_backward": [_vp, _vp, _vp, _vp, _i32, _u32, _vp, _vp, _vp, _i32, _vp],
+    "dfhip_resmlp_field_forward_dev": [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp],
+    "dfhip_resmlp_field_backward_dev": [_vp, _vp, _vp, _vp, _i32, _u32, _vp, _u32, _vp, _vp, _i32,
+                                        _vp],
     "dfhip_resmlp_render_rays_infer": [_u32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32,
                                        _u32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
                                        _vp],
@@ -203,6 +206,8 @@ _SIGS = {
     "dfhip_entropy_forward": [_u32, _vp, _f32, _vp, _vp],
     "dfhip_entropy_backward": [_u32, _vp, _vp, _f32, _vp, _vp],
     "dfhip_entropy_backward_accumulate": [_u32, _vp, _vp, _f32, _vp, _vp],
+    "dfhip_opacity_forward": [_u32, _vp, _f32, _vp, _i32, _vp],
+    "dfhip_opacity_backward_accumulate": [_u32, _vp, _vp, _f32, _vp, _vp],
     "dfhip_train_step_prologue": [_vp, _f32, _f32, _f32, _f32, _u32, _u32, _vp, _f32,
                                   ctypes.c_uint64, ctypes.c_uint64, _i32, _vp, _u32, _u32, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -282,6 +287,8 @@ def load() -> ctypes.CDLL:
     lib.dfhip_resmlp_params.argtypes = []
     lib.dfhip_resmlp_field_backward_scratch.restype = ctypes.c_uint64
     lib.dfhip_resmlp_field_backward_scratch.argtypes = [_u32]
+    lib.dfhip_resmlp_field_backward_dev_scratch.restype = ctypes.c_uint64
+    lib.dfhip_resmlp_field_backward_dev_scratch.argtypes = [_u32]
     lib.dfhip_voxel_field_backward_scratch.restype = ctypes.c_uint64
     lib.dfhip_voxel_field_backward_scratch.argtypes = [_u32, _u32]
     lib.dfhip_voxel_field_backward_dev_scratch.restype = ctypes.c_uint64
@@ -309,6 +316,7 @@ def exported_symbols() -> list[str]:
             "dfhip_grid_backward_default_parts", "dfhip_grid_backward_partial_floats",
             "dfhip_field_mlp_params", "dfhip_field_mlp_backward_parts",
             "dfhip_resmlp_params", "dfhip_resmlp_field_backward_scratch",
+            "dfhip_resmlp_field_backward_dev_scratch",
             "dfhip_voxel_field_backward_scratch", "dfhip_voxel_field_backward_dev_scratch",
             "dfhip_ray_head_partial_floats", "dfhip_march_rays_train_stage_floats",
             "dfhip_shading_partial_doubles", "dfhip_grid_backward_binned_tile",

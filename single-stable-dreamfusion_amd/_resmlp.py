@@ -124,3 +124,64 @@ def field_backward(xyz, params, grad_sigma, grad_albedo, dx=None, grads=None, ac
     call("dfhip_resmlp_field_backward", ptr(xyz), _pointers(params, "param"), ptr(grad_sigma),
          ptr(grad_albedo), _d.dtype_code(grad_albedo, "grad_albedo"), M, ptr(dx), ptr(scratch),
          None if grads is None else _pointers(grads, "grad"), int(bool(accumulate)), stream())
+
+
+# ---------------------------------------------------------------- device counts
+def backward_dev_scratch_bytes(cap):
+    """Bytes of field_backward_dev's scratch: 3392 bytes of tile state and 1232
+    neuron-major f16 rows per sample of the capacity, plus 64 partial images
+    of the gradients and 256 LayerNorm partials per 65536 rows."""
+    return int(_d.load().dfhip_resmlp_field_backward_dev_scratch(int(cap)))
+
+
+def _count(m_dev, align):
+    checked(m_dev, "m_dev", "int")
+    if m_dev.numel() < 1:
+        raise RuntimeError("m_dev must hold the live row count (int32)")
+    if int(align) < 1:
+        raise RuntimeError("align must be at least 1")
+
+
+def field_forward_dev(xyz, params, sigma, albedo, m_dev, align=1):
+    """field_forward on the rows [0, m_dev[0]) of capacity-sized buffers: xyz
+    [cap, 3], sigma [cap], albedo [cap, 3] f16; rows at or past the live count
+    are neither read nor written."""
+    cap = xyz.shape[0]
+    _f32(xyz, "xyz")
+    _f32(sigma, "sigma")
+    checked(albedo, "albedo")
+    _count(m_dev, align)
+    if tuple(xyz.shape) != (cap, 3) or tuple(sigma.shape) != (cap,) or \
+            tuple(albedo.shape) != (cap, 3) or albedo.dtype != torch.float16:
+        raise RuntimeError("xyz [cap, 3] f32, sigma [cap] f32 and albedo [cap, 3] f16 expected")
+    call("dfhip_resmlp_field_forward_dev", ptr(xyz), _pointers(params, "param"), ptr(sigma),
+         ptr(albedo), cap, ptr(m_dev), int(align), stream())
+
+
+def field_backward_dev(xyz, params, grad_sigma, grad_albedo, grads, m_dev, align=1,
+                       accumulate=False, scratch=None):
+    """field_backward's parameter gradients over min(cap, align_up(m_dev[0],
+    align)) rows of capacity-sized buffers, rows from the live count on taken
+    as zero padding (never read): the bits of field_backward on that many rows
+    with zeroed tail rows.  scratch: uint8 tensor of
+    backward_dev_scratch_bytes(cap) or None (allocated)."""
+    cap = xyz.shape[0]
+    _f32(xyz, "xyz")
+    _f32(grad_sigma, "grad_sigma")
+    checked(grad_albedo, "grad_albedo")
+    _count(m_dev, align)
+    if grad_albedo.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("grad_albedo must be float16 or float32")
+    if tuple(xyz.shape) != (cap, 3) or tuple(grad_sigma.shape) != (cap,) or \
+            tuple(grad_albedo.shape) != (cap, 3):
+        raise RuntimeError("xyz [cap, 3], grad_sigma [cap] and grad_albedo [cap, 3] expected")
+    need = backward_dev_scratch_bytes(cap)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=xyz.device)
+    checked(scratch, "scratch", "u8")
+    if scratch.numel() < need:
+        raise RuntimeError(f"scratch must hold {need} bytes")
+    call("dfhip_resmlp_field_backward_dev", ptr(xyz), _pointers(params, "param"),
+         ptr(grad_sigma), ptr(grad_albedo), _d.dtype_code(grad_albedo, "grad_albedo"), cap,
+         ptr(m_dev), int(align), ptr(scratch), _pointers(grads, "grad"), int(bool(accumulate)),
+         stream())

@@ -739,6 +739,43 @@ __global__ __launch_bounds__(256) void k_entropy_bwd(uint32_t N, const float *__
     grad_ws[n] = ACC ? grad_ws[n] + v : v;
 }
 
+// ---------------------------------------------------------------- opacity
+// lambda * mean(ws^2) by one 1024-thread block: f64 squares, summed in
+// entropy_loss_block's order (elements n, n + blockDim, ... per thread, the
+// wave's xor butterfly, the waves in order).
+__global__ __launch_bounds__(1024) void k_opacity_fwd(uint32_t N, const float *__restrict__ ws,
+                                                      float lambda, float *__restrict__ loss,
+                                                      int accumulate) {
+    __shared__ double part[16];
+    double s = 0.0;
+    for (uint32_t n = threadIdx.x; n < N; n += blockDim.x) {
+        const double w = (double)ws[n];
+        s += w * w;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += part[i];
+        const float v = (float)((double)lambda * t / (double)N);
+        loss[0] = accumulate ? loss[0] + v : v;
+    }
+}
+
+// grad_ws += ((g * lambda) / N) * (2 ws): autograd's chain of
+// lambda * (ws ** 2).mean(), each step one f32 rounding.
+__global__ __launch_bounds__(256) void k_opacity_bwd_acc(uint32_t N, const float *__restrict__ ws,
+                                                         const float *__restrict__ g, float lambda,
+                                                         float *__restrict__ grad_ws) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const float scale = f32_rounded(f32_rounded(g[0] * lambda) / (float)N);
+    const float v = f32_rounded(scale * (2.0f * ws[n]));
+    grad_ws[n] = grad_ws[n] + v;
+}
+
 }  // namespace hd
 }  // namespace dfhip
 
@@ -1041,4 +1078,28 @@ extern "C" int dfhip_entropy_backward_accumulate(uint32_t N, const float *ws,
     hd::k_entropy_bwd<true><<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(
         N, ws, grad_loss, lambda, grad_ws);
     return check_launch("entropy_backward_accumulate");
+}
+
+extern "C" int dfhip_opacity_forward(uint32_t N, const float *ws, float lambda, float *loss,
+                                     int accumulate, dfhip_stream_t stream) {
+    if (N == 0) return DFHIP_OK;
+    if (!ws || !loss) {
+        set_error("opacity_forward: null pointer");
+        return DFHIP_EINVAL;
+    }
+    hd::k_opacity_fwd<<<1, 1024, 0, as_stream(stream)>>>(N, ws, lambda, loss, accumulate ? 1 : 0);
+    return check_launch("opacity_forward");
+}
+
+extern "C" int dfhip_opacity_backward_accumulate(uint32_t N, const float *ws,
+                                                 const float *grad_loss, float lambda,
+                                                 float *grad_ws, dfhip_stream_t stream) {
+    if (N == 0) return DFHIP_OK;
+    if (!ws || !grad_loss || !grad_ws) {
+        set_error("opacity_backward_accumulate: null pointer");
+        return DFHIP_EINVAL;
+    }
+    hd::k_opacity_bwd_acc<<<ceil_div(N, 256u), 256, 0, as_stream(stream)>>>(N, ws, grad_loss,
+                                                                           lambda, grad_ws);
+    return check_launch("opacity_backward_accumulate");
 }

@@ -82,6 +82,104 @@ __global__ __launch_bounds__(64 * kFwdWaves) void k_resmlp_fwd(
     }
 }
 
+// ------------------------------------------------------------------ device counts
+// The device-count entries take their row count from the device: buffers hold
+// `cap` rows, *m_dev is the live count, so the launch shapes depend on the
+// capacity only and the launches capture into a graph (voxelfield.hip's
+// scheme).  Rows at or past the live count are neither read nor written.
+__device__ __forceinline__ uint32_t live_rows(const int32_t *m_dev, uint32_t cap) {
+    const int32_t m = *m_dev;
+    return m < 0 ? 0u : ((uint32_t)m < cap ? (uint32_t)m : cap);
+}
+
+// Rows the backward sums over: the live count rounded up to `align` (the
+// march's slice), at most the capacity.
+__device__ __forceinline__ uint32_t effective_rows(uint32_t m, uint32_t cap, uint32_t align) {
+    const uint64_t a = ((uint64_t)m + align - 1u) / align * align;
+    return a < (uint64_t)cap ? (uint32_t)a : cap;
+}
+
+__host__ __device__ inline uint32_t padded(uint32_t m) { return ceil_div(m, 32u) * 32u; }
+
+// Workgroups the host-count backward gives the gradient pass of a chunk of
+// `tiles` tiles (persistent_blocks(tiles, 8, kLnParts) on a device of `cus`
+// compute units): the number of LayerNorm-parameter partials of that chunk.
+__host__ __device__ inline uint32_t act_blocks(uint32_t tiles, uint32_t cus) {
+    const uint32_t want = ceil_div(tiles, 8u);
+    uint32_t n = want < cus ? want : cus;
+    if (n > kLnParts) n = kLnParts;
+    return n ? n : 1u;
+}
+
+// Chunk `chunk` of Me effective rows of a capacity of cap rows: the padded row
+// count, splits and gradient-pass workgroups the host loop gives it, and the
+// row stride of its neuron-major images (the capacity's share of the chunk).
+struct Chunk {
+    uint32_t mp, splits, nblk, ld;
+};
+__device__ __forceinline__ Chunk chunk_of(uint32_t chunk, uint32_t Me, uint32_t cap,
+                                          uint32_t cus) {
+    const uint32_t m0 = chunk * kChunk, left = cap - m0;
+    Chunk k;
+    k.mp = padded(Me - m0 < kChunk ? Me - m0 : kChunk);
+    k.splits = k.mp / 32u < kSplits ? k.mp / 32u : kSplits;
+    k.nblk = act_blocks(k.mp / 16u, cus);
+    k.ld = padded(left < kChunk ? left : kChunk);
+    return k;
+}
+
+// The neuron-major images of the device-count backward: chunk c's three images
+// (xrows, arows, grows, each of row stride Chunk::ld) start at rows + c *
+// kChunk * kRowsAll halves.
+constexpr int kRowsAll = kXRows + kARows + kGRows;
+
+// Forward with the device count.  SAVE false: sigma / albedo of rows [0, m).
+// SAVE true: the backward's saving forward over the tiles of the effective
+// rows (tile t of the capacity is tile t % 4096 of chunk t / 4096; rows at or
+// past the live count run as position 0, the host-count entry's padding).
+template <bool SAVE>
+__global__ __launch_bounds__(64 * kFwdWaves) void k_resmlp_fwd_dev(
+    const float *__restrict__ xyz, Ptrs P, float *__restrict__ sigma,
+    half_t *__restrict__ albedo, uint32_t cap, const int32_t *__restrict__ m_dev,
+    uint32_t align, u32x4 *__restrict__ state, half_t *__restrict__ rows) {
+    __shared__ FwdW W;
+    load_fwd_weights(W, P);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, c = lane & 15, h = lane >> 4;
+    const uint32_t M = live_rows(m_dev, cap);
+    const uint32_t Me = SAVE ? effective_rows(M, cap, align) : M;
+    const uint32_t tiles = SAVE ? padded(Me) / 16u : ceil_div(M, 16u);
+    const uint32_t waves = gridDim.x * kFwdWaves;
+    for (uint32_t tile = blockIdx.x * kFwdWaves + (threadIdx.x >> 6); tile < tiles;
+         tile += waves) {
+        asm volatile("" ::: "memory");  // as k_resmlp_fwd
+        const uint32_t sample = tile * 16 + c;
+        const bool valid = sample < M;
+        float x[3] = {0.0f, 0.0f, 0.0f};
+        if (valid)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) x[d] = xyz[(size_t)sample * 3 + d];
+        float ho[4];
+        if constexpr (SAVE) {
+            const uint32_t chunk = tile / (kChunk / 16u);
+            const uint32_t left = cap - chunk * kChunk;
+            const size_t ld = padded(left < kChunk ? left : kChunk);
+            half_t *img = rows + (size_t)chunk * kChunk * kRowsAll;
+            forward_tile(W, x, c, h, ho, state + (size_t)tile * kStTile * 64 + lane, img,
+                         img + (size_t)kXRows * ld, ld, sample - chunk * kChunk);
+        } else {
+            forward_tile(W, x, c, h, ho, nullptr, nullptr, nullptr, 0, sample);
+            if (!valid) continue;
+            if (h == 0) {
+                sigma[sample] = expf(ho[0] + fm::gaussian(x));
+            } else {
+                const float v = h == 1 ? ho[1] : (h == 2 ? ho[2] : ho[3]);
+                albedo[(size_t)sample * 3 + h - 1] = (half_t)sigmoidf(v);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ gradient pass
 // Transposed weights [n_in][n_out] of layers 1..3, and with DX of layer 0's
 // dense and skip projections ([64][128], rows 39..63 zero); the output layer
@@ -117,23 +215,87 @@ __device__ inline void load_bwd_weights(BwdW<DX> &W, const Ptrs &P) {
 // gradients for the weight-gradient products (grows, neuron-major [row][Mp])
 // and this workgroup's LayerNorm parameter gradients (lnpart [gridDim.x]
 // [block][gamma | beta][128]).  ga_t: grad_albedo's type.
-template <bool DX, bool WG, int WAVES, typename ga_t>
+// Device count (DEV; parameter gradients only, DX false): the host-count entry
+// gives chunk k of the effective rows Chunk::nblk workgroups, workgroup b's
+// wave w the tiles 8 b + w, + 8 nblk, ... of the chunk, and one LayerNorm
+// partial per workgroup.  A workgroup of the DEV launch plays workgroup b =
+// blockIdx.x (+ gridDim.x, ...) of every live chunk in turn: the same tiles in
+// the same order into freshly zeroed sums, the same wave-ordered partial, at
+// lnpart [chunk][kLnParts][block][gamma | beta][128].  The grid is the
+// capacity's (a full chunk's workgroups from 32768 rows on), so a workgroup
+// takes at most one role per chunk, as the host-count launch gives it.  The
+// per-chunk arguments (xyz .. Mp) are then unused: they come from `dev`.
+template <bool DEV>
+struct DevCount {};
+template <>
+struct DevCount<true> {
+    const float *xyz, *grad_sigma;
+    const void *grad_albedo;
+    const u32x4 *state;
+    half_t *rows;
+    const int32_t *m_dev;
+    uint32_t cap, align, cus;
+};
+template <bool DEV>
+struct DevRole {};
+template <>
+struct DevRole<true> {
+    uint32_t live, Me, chunk, b;
+    bool started;
+    Chunk k;
+    __device__ __forceinline__ void begin(const DevCount<true> &d) {
+        live = live_rows(d.m_dev, d.cap), Me = effective_rows(live, d.cap, d.align);
+        chunk = 0, b = 0, started = false;
+    }
+    // workgroup-uniform: the roles b = block, block + grid, ... of chunk 0, then chunk 1, ...
+    __device__ __forceinline__ bool next(const DevCount<true> &d, uint32_t block, uint32_t grid) {
+        b = started ? b + grid : block;
+        started = true;
+        for (; chunk * kChunk < Me; ++chunk, b = block) {
+            k = chunk_of(chunk, Me, d.cap, d.cus);
+            if (b < k.nblk) return true;
+        }
+        return false;
+    }
+};
+
+template <bool DX, bool WG, int WAVES, typename ga_t, bool DEV = false>
 __global__ __launch_bounds__(64 * WAVES) void k_resmlp_bwd_act(
     const float *__restrict__ xyz, Ptrs P, const float *__restrict__ grad_sigma,
     const ga_t *__restrict__ grad_albedo, uint32_t M, uint32_t tiles,
     const u32x4 *__restrict__ state, half_t *__restrict__ grows, uint32_t Mp,
-    float *__restrict__ lnpart, float *__restrict__ dx) {
+    float *__restrict__ lnpart, float *__restrict__ dx, DevCount<DEV> dev) {
     __shared__ BwdW<DX> W;
     __shared__ __attribute__((aligned(16))) float lnacc[WG ? WAVES : 1][kBlocks][2][kHid];
     load_bwd_weights(W, P);
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63, c = lane & 15, h = lane >> 4;
+    // the role of this workgroup: its first tile, the tile stride, its partial
+    uint32_t first = blockIdx.x * WAVES + wave, waves = gridDim.x * WAVES;
+    float *lnout = lnpart + (size_t)blockIdx.x * (kBlocks * 2 * kHid);
+    DevRole<DEV> role;
+    if constexpr (DEV) role.begin(dev);
+    do {  // once (host count), or once per role (DEV); the body keeps its indentation
+    if constexpr (DEV) {
+        // the next (chunk, workgroup) role of the host-count launches
+        if (!role.next(dev, blockIdx.x, gridDim.x)) break;
+        const uint32_t m0 = role.chunk * kChunk;
+        xyz = dev.xyz + (size_t)m0 * 3, grad_sigma = dev.grad_sigma + m0;
+        grad_albedo = (const ga_t *)dev.grad_albedo + (size_t)m0 * 3;
+        M = role.live > m0 ? (role.live - m0 < kChunk ? role.live - m0 : kChunk) : 0u;
+        tiles = role.k.mp / 16u, Mp = role.k.ld;
+        state = dev.state + (size_t)(m0 / 16u) * kStTile * 64;
+        grows = dev.rows + (size_t)role.chunk * kChunk * kRowsAll +
+                (size_t)(kXRows + kARows) * role.k.ld;
+        first = role.b * WAVES + wave, waves = role.k.nblk * WAVES;
+        lnout = lnpart + ((size_t)role.chunk * kLnParts + role.b) * (kBlocks * 2 * kHid);
+        __syncthreads();  // the last role's partial is read (first: nothing to wait for)
+    }
     if (WG)
         for (int i = threadIdx.x; i < WAVES * kBlocks * 2 * kHid; i += blockDim.x)
             (&lnacc[0][0][0][0])[i] = 0.0f;
     __syncthreads();
-    const uint32_t waves = gridDim.x * WAVES;
-    for (uint32_t tile = blockIdx.x * WAVES + wave; tile < tiles; tile += waves) {
+    for (uint32_t tile = first; tile < tiles; tile += waves) {
         asm volatile("" ::: "memory");  // no hoisting of the LDS operands (see k_resmlp_fwd)
         const uint32_t sample = tile * 16 + c;
         const bool valid = sample < M;
@@ -317,9 +479,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_resmlp_bwd_act(
         for (int i = threadIdx.x; i < kBlocks * 2 * kHid; i += blockDim.x) {
             float s = 0.0f;
             for (int w = 0; w < WAVES; ++w) s += (&lnacc[w][0][0][0])[i];
-            lnpart[(size_t)blockIdx.x * (kBlocks * 2 * kHid) + i] = s;
+            lnout[i] = s;
         }
     }
+    } while (DEV);
 }
 
 // ------------------------------------------------------------------ weight gradients
@@ -332,13 +495,16 @@ __global__ __launch_bounds__(64 * WAVES) void k_resmlp_bwd_act(
 // layers 1..3, 40 the output layer.
 constexpr int kJobs = 41;
 
-__global__ __launch_bounds__(64) void k_resmlp_wgrad(const half_t *__restrict__ xrows,
-                                                     const half_t *__restrict__ arows,
-                                                     const half_t *__restrict__ grows,
-                                                     uint32_t Mp, float *__restrict__ partial) {
+// wgrad_chunk: one chunk's product of wave (job, split) out of `splits`:
+// images of row stride Mp, mp / 32 k-steps.
+__device__ __forceinline__ void wgrad_chunk(const half_t *__restrict__ xrows,
+                                            const half_t *__restrict__ arows,
+                                            const half_t *__restrict__ grows, uint32_t Mp,
+                                            uint32_t mp, uint32_t split, uint32_t splits,
+                                            float *__restrict__ partial) {
     const int job = blockIdx.x, lane = threadIdx.x, c = lane & 15, h = lane >> 4;
-    const uint32_t split = blockIdx.y, ksteps = Mp / 32u;
-    const uint32_t per = ceil_div(ksteps, (uint32_t)gridDim.y);
+    const uint32_t ksteps = mp / 32u;
+    const uint32_t per = ceil_div(ksteps, splits);
     const uint32_t k0 = split * per < ksteps ? split * per : ksteps;
     const uint32_t k1 = k0 + per < ksteps ? k0 + per : ksteps;
     const half_t *G, *B;
@@ -401,6 +567,30 @@ __global__ __launch_bounds__(64) void k_resmlp_wgrad(const half_t *__restrict__ 
     }
 }
 
+__global__ __launch_bounds__(64) void k_resmlp_wgrad(const half_t *__restrict__ xrows,
+                                                     const half_t *__restrict__ arows,
+                                                     const half_t *__restrict__ grows,
+                                                     uint32_t Mp, float *__restrict__ partial) {
+    wgrad_chunk(xrows, arows, grows, Mp, Mp, blockIdx.y, gridDim.y, partial);
+}
+
+// Device count: wave (job, split) takes its share of every live chunk in turn;
+// chunk c has kSplits partial images at partial + c * kSplits * kParams.
+__global__ __launch_bounds__(64) void k_resmlp_wgrad_dev(const half_t *__restrict__ rows,
+                                                         uint32_t cap,
+                                                         const int32_t *__restrict__ m_dev,
+                                                         uint32_t align,
+                                                         float *__restrict__ partial) {
+    const uint32_t Me = effective_rows(live_rows(m_dev, cap), cap, align);
+    for (uint32_t chunk = 0; chunk * kChunk < Me; ++chunk) {
+        const Chunk k = chunk_of(chunk, Me, cap, 1u);  // (nblk unused)
+        if (blockIdx.y >= k.splits) continue;
+        const half_t *img = rows + (size_t)chunk * kChunk * kRowsAll;
+        wgrad_chunk(img, img + (size_t)kXRows * k.ld, img + (size_t)(kXRows + kARows) * k.ld, k.ld,
+                    k.mp, blockIdx.y, k.splits, partial + (size_t)chunk * kSplits * kParams);
+    }
+}
+
 // Fixed-order sums into the f32 gradients: a block takes 64 parameters; its
 // 16 part-lanes add the parts p = j, j + 16, ... in that order, then lane
 // j = 0 adds the 16 lane sums in order (as fieldmlp.hip's k_field_wgrad_sum).
@@ -446,9 +636,62 @@ __global__ __launch_bounds__(1024) void k_resmlp_reduce(const float *__restrict_
     dst[k] = accumulate ? dst[k] + s : s;
 }
 
-// ------------------------------------------------------------------ host side
-static uint32_t padded(uint32_t m) { return ceil_div(m, 32u) * 32u; }
+// Device count: the chunks' sums in chunk order, each formed as above (the
+// chunk's own split and workgroup counts) and added to the running f32 value
+// as the host loop's launches add it in memory.  No live chunk: zeros, or
+// nothing with accumulate.
+__global__ __launch_bounds__(1024) void k_resmlp_reduce_dev(const float *__restrict__ partial,
+                                                            const float *__restrict__ lnpart,
+                                                            uint32_t cap,
+                                                            const int32_t *__restrict__ m_dev,
+                                                            uint32_t align, uint32_t cus, GPtrs G,
+                                                            int accumulate) {
+    __shared__ float lane_sum[16][64];
+    const uint32_t Me = effective_rows(live_rows(m_dev, cap), cap, align);
+    const int col = threadIdx.x & 63, j = threadIdx.x >> 6;
+    const int i = blockIdx.x * 64 + col;
+    int ti = 0, k = 0;
+    bool ln = false;
+    size_t src0 = 0;
+    if (i < kParams) {
+        int off = 0;
+        for (int t = 0; t < kTensors; ++t) {
+            const int sz = t_size(t);
+            if (i >= off && i < off + sz) ti = t, k = i - off;
+            off += sz;
+        }
+        const int l = ti < 5 ? 0 : (ti < kTOutW ? 1 + (ti - 5) / 4 : -1);
+        const int w = ti < 5 ? ti : (ti < kTOutW ? (ti - 5) % 4 : -1);
+        ln = l >= 0 && (w == 2 || w == 3);
+        src0 = ln ? (size_t)(l * 2 + (w - 2)) * kHid + k : (size_t)i;
+    }
+    const bool writer = j == 0 && i < kParams;
+    float *dst = G.p[ti];
+    float v = 0.0f;
+    if (writer && accumulate) v = dst[k];
+    for (uint32_t chunk = 0; chunk * kChunk < Me; ++chunk) {  // block-uniform
+        const Chunk ck = chunk_of(chunk, Me, cap, cus);
+        const float *src = ln ? lnpart + (size_t)chunk * kLnParts * (kBlocks * 2 * kHid) + src0
+                              : partial + (size_t)chunk * kSplits * kParams + src0;
+        const size_t stride = ln ? kBlocks * 2 * kHid : kParams;
+        const uint32_t parts = ln ? ck.nblk : ck.splits;
+        float s = 0.0f;
+        if (i < kParams)
+            for (uint32_t p = j; p < parts; p += 16) s += src[(size_t)p * stride];
+        lane_sum[j][col] = s;
+        __syncthreads();
+        if (writer) {
+            s = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) s += lane_sum[q][col];
+            v = (accumulate || chunk > 0) ? v + s : s;
+        }
+        __syncthreads();  // lane_sum is rewritten next
+    }
+    if (writer && !(accumulate && Me == 0)) dst[k] = v;
+}
 
+// ------------------------------------------------------------------ host side
 // scratch layout for a chunk of mp (padded) samples; all sizes are multiples
 // of 16 bytes
 struct Scratch {
@@ -467,6 +710,24 @@ static Scratch scratch_layout(uint32_t mp) {
     return s;
 }
 
+// Device count: the tile state and the three neuron-major images of every
+// chunk of the capacity (cap rounded up to 32), then per 65536-row chunk
+// kSplits partial images of the gradients and kLnParts LayerNorm partials.
+struct ScratchDev {
+    size_t state, rows, partial, lnpart, total;
+};
+static ScratchDev scratch_layout_dev(uint32_t cap) {
+    ScratchDev s;
+    const size_t capp = ceil_div((size_t)cap, (size_t)32) * 32, chunks = ceil_div(cap, kChunk);
+    size_t o = 0;
+    s.state = o, o += capp / 16 * kStTile * 64 * sizeof(u32x4);
+    s.rows = o, o += (size_t)kRowsAll * capp * sizeof(half_t);
+    s.partial = o, o += chunks * kSplits * kParams * sizeof(float);
+    s.lnpart = o, o += chunks * kLnParts * kBlocks * 2 * kHid * sizeof(float);
+    s.total = o ? o : 16;
+    return s;
+}
+
 static uint32_t persistent_blocks(uint32_t tiles, int waves, uint32_t cap) {
     const uint32_t want = ceil_div(tiles, (uint32_t)waves), cus = device_cus();
     uint32_t n = want < cus ? want : cus;
@@ -481,10 +742,10 @@ static void launch_bwd_act(hipStream_t s, uint32_t nblk, const float *xyz, const
                            float *lnpart, float *dx) {
     if (ga_dtype == DFHIP_F16)
         k_resmlp_bwd_act<DX, WG, WAVES, half_t><<<nblk, 64 * WAVES, 0, s>>>(
-            xyz, P, gs, (const half_t *)ga, m, tiles, state, grows, mp, lnpart, dx);
+            xyz, P, gs, (const half_t *)ga, m, tiles, state, grows, mp, lnpart, dx, DevCount<false>{});
     else
         k_resmlp_bwd_act<DX, WG, WAVES, float><<<nblk, 64 * WAVES, 0, s>>>(
-            xyz, P, gs, (const float *)ga, m, tiles, state, grows, mp, lnpart, dx);
+            xyz, P, gs, (const float *)ga, m, tiles, state, grows, mp, lnpart, dx, DevCount<false>{});
 }
 
 }  // namespace rs
@@ -612,5 +873,112 @@ extern "C" int dfhip_resmlp_field_backward(const float *xyz, const float *const 
         k_resmlp_reduce<<<ceil_div((uint32_t)kParams, 64u), 1024, 0, s>>>(
             partial, splits, lnpart, nblk, G, (accumulate || m0 > 0) ? 1 : 0);
     }
+    return check_launch(name);
+}
+
+// ------------------------------------------------------------------ device-count entries
+// The checks of the device-count forms' own arguments.
+static bool device_count(const char *name, uint32_t cap, const int32_t *m_dev, uint32_t align) {
+    if (cap > 0x7fffffffu) {
+        set_error("%s: the capacity must be below 2^31 rows, got %u", name, cap);
+        return false;
+    }
+    if (!m_dev) {
+        set_error("%s: m_dev is null", name);
+        return false;
+    }
+    if (align == 0) {
+        set_error("%s: align must be at least 1", name);
+        return false;
+    }
+    return true;
+}
+
+extern "C" int dfhip_resmlp_field_forward_dev(const float *xyz, const float *const *params,
+                                              float *sigma, void *albedo, uint32_t cap,
+                                              const int32_t *m_dev, uint32_t align,
+                                              dfhip_stream_t stream) {
+    const char *name = "resmlp_field_forward_dev";
+    Ptrs P;
+    if (!gather(name, params, P)) return DFHIP_EINVAL;
+    if (!device_count(name, cap, m_dev, align)) return DFHIP_EINVAL;
+    if (cap == 0) return DFHIP_OK;
+    if (!xyz || !sigma || !albedo) {
+        set_error("%s: null pointer", name);
+        return DFHIP_EINVAL;
+    }
+    // the launch shape of the capacity; the kernel stops at the live tiles
+    const uint32_t tiles = ceil_div(cap, 16u);
+    k_resmlp_fwd_dev<false><<<persistent_blocks(tiles, kFwdWaves, 65535u), 64 * kFwdWaves, 0,
+                              as_stream(stream)>>>(xyz, P, sigma, (half_t *)albedo, cap, m_dev,
+                                                   align, nullptr, nullptr);
+    return check_launch(name);
+}
+
+extern "C" uint64_t dfhip_resmlp_field_backward_dev_scratch(uint32_t cap) {
+    return (uint64_t)scratch_layout_dev(cap).total;
+}
+
+extern "C" int dfhip_resmlp_field_backward_dev(const float *xyz, const float *const *params,
+                                               const float *grad_sigma, const void *grad_albedo,
+                                               int grad_albedo_dtype, uint32_t cap,
+                                               const int32_t *m_dev, uint32_t align,
+                                               void *scratch, float *const *grads,
+                                               int accumulate, dfhip_stream_t stream) {
+    const char *name = "resmlp_field_backward_dev";
+    Ptrs P;
+    if (!gather(name, params, P)) return DFHIP_EINVAL;
+    GPtrs G;
+    if (!grads) {
+        set_error("%s: null gradient list", name);
+        return DFHIP_EINVAL;
+    }
+    for (int t = 0; t < kTensors; ++t) {
+        if (!grads[t]) {
+            set_error("%s: gradient %d is null", name, t);
+            return DFHIP_EINVAL;
+        }
+        G.p[t] = grads[t];
+    }
+    if (grad_albedo_dtype != DFHIP_F16 && grad_albedo_dtype != DFHIP_F32) {
+        set_error("%s: grad_albedo dtype must be f16 or f32", name);
+        return DFHIP_EDTYPE;
+    }
+    if (!device_count(name, cap, m_dev, align)) return DFHIP_EINVAL;
+    if (!scratch || ((uintptr_t)scratch & 15u)) {
+        set_error("%s: scratch must be a 16-byte aligned buffer of "
+                  "dfhip_resmlp_field_backward_dev_scratch(cap) bytes", name);
+        return DFHIP_EINVAL;
+    }
+    if (cap && (!xyz || !grad_sigma || !grad_albedo)) {
+        set_error("%s: null pointer", name);
+        return DFHIP_EINVAL;
+    }
+    hipStream_t s = as_stream(stream);
+    const ScratchDev L = scratch_layout_dev(cap);
+    char *base = (char *)scratch;
+    u32x4 *state = (u32x4 *)(base + L.state);
+    half_t *rows = (half_t *)(base + L.rows);
+    float *partial = (float *)(base + L.partial), *lnpart = (float *)(base + L.lnpart);
+    const uint32_t cus = device_cus();
+    if (cap) {
+        // launch shapes of the capacity; the kernels stop at the live chunks
+        const uint32_t tiles = ceil_div(cap, 32u) * 2u;
+        k_resmlp_fwd_dev<true><<<persistent_blocks(tiles, kFwdWaves, 65535u), 64 * kFwdWaves, 0,
+                                 s>>>(xyz, P, nullptr, nullptr, cap, m_dev, align, state, rows);
+        const uint32_t nblk = persistent_blocks(tiles, 8, kLnParts);
+        const DevCount<true> dev{xyz, grad_sigma, grad_albedo, state, rows, m_dev, cap, align, cus};
+        if (grad_albedo_dtype == DFHIP_F16)
+            k_resmlp_bwd_act<false, true, 8, half_t, true><<<nblk, 64 * 8, 0, s>>>(
+                nullptr, P, nullptr, nullptr, 0u, 0u, nullptr, nullptr, 0u, lnpart, nullptr, dev);
+        else
+            k_resmlp_bwd_act<false, true, 8, float, true><<<nblk, 64 * 8, 0, s>>>(
+                nullptr, P, nullptr, nullptr, 0u, 0u, nullptr, nullptr, 0u, lnpart, nullptr, dev);
+        const uint32_t first = padded(cap < kChunk ? cap : kChunk);
+        const uint32_t splits = first / 32u < kSplits ? first / 32u : kSplits;
+        k_resmlp_wgrad_dev<<<dim3(kJobs, splits), 64, 0, s>>>(rows, cap, m_dev, align, partial);
+    }
+    k_resmlp_reduce_dev<<<ceil_div((uint32_t)kParams, 64u), 1024, 0, s>>>(
+        partial, lnpart, cap, m_dev, align, cus, G, accumulate ? 1 : 0);
     return check_launch(name);
 }

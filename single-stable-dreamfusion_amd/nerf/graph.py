@@ -31,6 +31,9 @@ steps (finite-difference normals, csrc/shade.hip) only as the native step.  The
 DVGO backbone's steps are captured only as its own native step
 (nerf/native_voxel_step.py: the same capture, NativeVoxelStep in the place of
 NativeAlbedoStep; its background network's autograd is recorded in the graph).
+The vanilla backbone's albedo step is captured as its native step
+(nerf/native_vanilla_step.py) where that applies, else in the autograd form;
+its shaded steps run eagerly.
 RNG draws inside the graph (march noise, background colour, light direction,
 timestep, SDS noise) use torch's graph-safe Philox offsets, so every replay
 draws fresh numbers.
@@ -43,6 +46,7 @@ import torch
 import _dfhip
 from . import field as _field
 from . import native_step as _native
+from . import native_vanilla_step as _vanilla
 from . import native_voxel_step as _voxel
 
 
@@ -81,6 +85,12 @@ class GraphedTrainStep:
                 raise RuntimeError("the dvgo backbone's step is graphed only as the native "
                                    "voxel step (nerf/native_voxel_step.py eligible())")
             self.native = _voxel.NativeVoxelStep(trainer, self.H, self.W, shading, ambient_ratio)
+        elif _vanilla.serves(trainer.model):
+            # the vanilla backbone: its native albedo step where it applies,
+            # else the autograd form below
+            if posed and _vanilla.eligible(trainer, shading):
+                self.native = _vanilla.NativeVanillaStep(trainer, self.H, self.W, shading,
+                                                         ambient_ratio)
         elif posed and _native.eligible(trainer, shading):
             self.native = _native.NativeAlbedoStep(trainer, self.H, self.W, shading,
                                                    ambient_ratio)

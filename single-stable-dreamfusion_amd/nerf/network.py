@@ -21,9 +21,15 @@ on, and `native_render_calls` counts the frames (each also counts once in
 `native_calls`, where the host loop makes one call per iteration);
 `native_infer = False` returns to the host loop.  Not covered: the three
 shaded views (their normal is the MLP's input gradient; they keep the host
-loop on the native field and normal), the background MLP (a LayerNorm ResBlock
-net the native ray head does not evaluate: native_background_layers returns
-None) and the native train step.
+loop on the native field and normal) and the background MLP (a LayerNorm
+ResBlock net the native ray head does not evaluate: native_background_layers
+returns None).
+Under Trainer(graph_step=True) the albedo train step replays as a graph of
+native launches (nerf/native_vanilla_step.py: the device-count forms of the
+field, the opacity regulariser, GradScaler + Adam in the graph), and
+`native_step_calls` counts the steps so served; shaded train steps need the
+parameter gradient of the MLP's input gradient and stay on the eager autograd
+step.
 The reference's NeRFNetwork_Kailu wrapper of this file is nerf/network_dvgo.py.
 """
 import torch
@@ -87,6 +93,8 @@ class NeRFNetwork(NeRFRenderer):
         self.native_calls = self.native_normal_calls = self.torch_calls = 0
         # eval frames rendered by the fused persistent launch (csrc/resmlprender.hip)
         self.native_render_calls = 0
+        # train steps served by the native step (nerf/native_vanilla_step.py)
+        self.native_step_calls = 0
         if self.bg_radius > 0:
             self.num_layers_bg = num_layers_bg
             self.hidden_dim_bg = hidden_dim_bg

@@ -617,6 +617,9 @@ class Trainer(object):
             # samples gathers by boolean masks, which synchronise with the host
             from . import native_voxel_step as _voxel
             return self.native_step and _voxel.eligible(self, shading)
+        from . import native_vanilla_step as _vanilla
+        if self.native_step and _vanilla.serves(self.model) and _vanilla.eligible(self, shading):
+            return True  # the vanilla backbone's native albedo step
         if not self.fused_backward or shading != "albedo" or self.bf16:
             # the two-pass backward and the normal-shaded steps are graphed only
             # as the native step
