@@ -1235,7 +1235,38 @@ int dfhip_opacity_backward_accumulate(uint32_t N, const float *ws, const float *
  * eps ~ N(0,1) (nerf/sd.py InjectedSDS; NULL to skip) and counter[0..1] = 0
  * (renderer.py:470; NULL to skip).  Random numbers: Philox4x32-10 keyed by
  * `seed`, counter (ray, step, stream) — fresh per step index, independent of
- * the launch shape. */
+ * the launch shape.  pose and aabb are HOST arrays; every output is device
+ * memory.
+ *
+ * The draw (f32 throughout; lo / hi the 32-bit halves of the 64-bit seed and
+ * step; every recorded trajectory depends on it, so it is fixed):
+ *   unit(v)  = (v >> 8) 2^-24        in [0, 1), exact in f32;
+ *   unit1(v) = ((v >> 8) + 1) 2^-24  in (0, 1], the argument of the log;
+ *   per ray n (the pixel index h W + w, so the first rays of a larger image
+ *   draw what a smaller one draws), with key = (seed_lo, seed_hi):
+ *     r0 = Philox4x32-10(counter = (n, step_lo, step_hi, 0), key),
+ *     r1 = Philox4x32-10(counter = (n, step_lo, step_hi, 1), key);
+ *     noises[n]   = unit(r0.x), or 0 unless perturb;
+ *     bg_color[n] = (unit(r0.w), unit(r1.z), unit(r1.w));
+ *     Box-Muller:   ra = sqrt(-2 log(unit1(r0.y))), angle a0 = 2 pi unit(r0.z),
+ *                   rb = sqrt(-2 log(unit1(r1.x))), angle a1 = 2 pi unit(r1.y)
+ *                   (2 pi as the f32 constant 6.2831855);
+ *     eps[n]      = (ra cos a0, ra sin a0, rb cos a1); rb sin a1 is not used,
+ *                   so every one of the eight words feeds one value;
+ *   per step, the same in every ray:
+ *     rt = Philox4x32-10(counter = (0xFFFFFFFF, step_lo, step_hi, 2), key),
+ *     t  = min_step + rt.x % (max_step - min_step + 1) (the modulo's bias
+ *          towards small t, below 2^-32 (max_step - min_step + 1), is part of
+ *          the draw; alphas must hold max_step + 1 values);
+ *     g_image[c N + n] = (1 - alphas[t]) * eps[n][c], channel-major.
+ * The light of the shaded steps (dfhip_shading_light) uses counter
+ * (0xFFFFFFFE, step_lo, step_hi, 3) of the same key.
+ *
+ * counter, lr_dev and row_dev (the _lr and _row forms below) are written even
+ * when H * W = 0: one block still runs, and the ray buffers are not touched.
+ * Refused with DFHIP_EINVAL and no launch: a null pose, aabb, rays_o, rays_d,
+ * nears or fars; a zero fx or fy; g_image without alphas or with max_step <
+ * min_step; n_lr > 8, or n_lr > 0 with a null lr_host or lr_dev; H * W >= 2^32. */
 int dfhip_train_step_prologue(const float *pose, float fx, float fy, float cx, float cy,
                               uint32_t H, uint32_t W, const float *aabb, float min_near,
                               uint64_t seed, uint64_t step, int perturb, const float *alphas,
