@@ -59,8 +59,12 @@ def nets(gpu):
     dense = copy.deepcopy(base)
     with torch.no_grad():  # sigma ~ e^6: T < 1e-4 after a sample or two
         dense.sigma_net.net[4].bias[0] += 6.0
+    # the trained-like head of tests/field_head_cases.py: h0 + gaussian spans
+    # about [-70, 70] and a third of the albedo entries are exactly 0 or 1
+    import field_head_cases as fc
+    trained = fc.load_params(make_net(gpu), fc.vanilla_case()["trained"])
     out = {"base": base, "dense": dense, "bound2": make_net(gpu, 1, args=("--bound", "2")),
-           "narrow": make_net(gpu, 2, hidden_dim=64)}
+           "narrow": make_net(gpu, 2, hidden_dim=64), "trained": trained}
     assert out["base"].cascade == 1 and out["bound2"].cascade == 2
     return out
 
@@ -178,6 +182,18 @@ def test_random_bitfield(gpu, nets):
     set_bits(net, "ones")
     _, full = fused(net, rays_o, rays_d)
     assert 0 < samples < full // 2  # most of the box is skipped
+
+
+def test_trained_head_frame(gpu, nets):
+    """A frame through a field whose density spans e^-70 .. e^70 (empty space
+    beside solid cells along one ray) and whose colours saturate: the loop's
+    bits all the same."""
+    net = nets["trained"]
+    set_bits(net, "ones")
+    rays_o, rays_d = rays(gpu, 16, 16, seed=8)
+    got, samples = both(net, rays_o, rays_d, "trained head")
+    assert samples > 256
+    assert (got[0] > 0.99).any()  # some ray met a solid cell
 
 
 # ---------------------------------------------------------------- 3, 4: ray counts
