@@ -1007,6 +1007,9 @@ typedef struct dfhip_binned_opts {
                                    with stencil groups.  Read for rows < *m_dev only, by
                                    the binning: a phase-1 call with a mask must run after
                                    the field backward that writes it */
+    const uint8_t *row_live_bytes; /* NULL = off.  row_live with one byte per row (nonzero:
+                                   live), as dfhip_ray_chain_train_live writes it; same
+                                   rules.  DFHIP_EINVAL together with row_live */
 } dfhip_binned_opts;
 /* dfhip_grid_backward_binned_scratch / dfhip_grid_encode_backward_binned_stencil
  * with per-call options (group 1 = single samples, eps ignored; group 7 =
@@ -1193,6 +1196,24 @@ int dfhip_ray_chain_train(
     float *gw1, float *gb1, float *gw2, float *gb2, const float *grad_loss, float lambda,
     float *loss, float *found_inf, int defer_sum, float *grad_sigmas, void *grad_rgbs,
     dfhip_stream_t stream);
+/* dfhip_ray_chain_train that also writes the rows' liveness mask for the
+ * binned embedding backward (dfhip_binned_opts.row_live_bytes), one byte per
+ * row: beside each taken sample's gradient stores, 1 iff its grad_sigmas value
+ * or one of its three grad_rgbs values (as stored, i.e. rounded to rgb_dtype)
+ * compares unequal to zero (-0.0 is zero, a NaN is live), the test of
+ * dfhip_grid_field_backward_check_live; 0 for the rows it zero-fills.  So the
+ * bytes of exactly the rows whose gradients the call writes are written: every
+ * row below the march's sample count (clipped to M).  row_live_bytes [M], not
+ * NULL. */
+int dfhip_ray_chain_train_live(
+    int rgb_dtype, const float *sigmas, const void *rgbs, const float *deltas,
+    const int32_t *rays, uint32_t M, uint32_t N, float T_thresh, float *ws, float *depth,
+    float *image, const float *rays_d, const float *nears, const float *fars, const float *w1,
+    const float *b1, const float *w2, const float *b2, float *out_image, float *out_depth,
+    uint8_t *mask, const float *g_image, float *grad_image, float *grad_ws, float *partial,
+    float *gw1, float *gb1, float *gw2, float *gb2, const float *grad_loss, float lambda,
+    float *loss, float *found_inf, int defer_sum, float *grad_sigmas, void *grad_rgbs,
+    uint8_t *row_live_bytes, dfhip_stream_t stream);
 
 /* nerf/utils.py:386-391 entropy regulariser: loss[0] = lambda * mean(-a log2 a
  * - (1 - a) log2(1 - a)), a = clamp(ws, 1e-5, 1 - 1e-5) (f64 sum); backward

@@ -177,6 +177,8 @@ _SIGS = {
                                                                                  _i32, _vp],
     "dfhip_ray_chain_train": [_i32] + [_vp] * 4 + [_u32, _u32, _f32] + [_vp] * 22 + [
         _f32, _vp, _vp, _i32, _vp, _vp, _vp],
+    "dfhip_ray_chain_train_live": [_i32] + [_vp] * 4 + [_u32, _u32, _f32] + [_vp] * 22 + [
+        _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "dfhip_param_grad_sums": [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _u32, _vp, _vp, _vp,
                               _vp, _vp, _vp, _f32, _vp, _vp, _vp],
     "dfhip_grid_field_backward_check": [_i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

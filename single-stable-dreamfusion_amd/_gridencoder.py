@@ -149,14 +149,16 @@ class BinnedOpts(ctypes.Structure):
     _fields_ = [("walk_mode", ctypes.c_int32), ("fast_bin", ctypes.c_int32),
                 ("walk_groups_per_cu", ctypes.c_int32), ("lane_perm", ctypes.c_int32),
                 ("kept_clean", ctypes.c_int32), ("trace", ctypes.c_void_p),
-                ("found_inf", ctypes.c_void_p), ("row_live", ctypes.c_void_p)]
+                ("found_inf", ctypes.c_void_p), ("row_live", ctypes.c_void_p),
+                ("row_live_bytes", ctypes.c_void_p)]
 
     def __init__(self, walk_mode=-1, fast_bin=-1, walk_groups_per_cu=0, lane_perm=-1,
-                 trace=None, kept_clean=0, found_inf=None, row_live=None):
+                 trace=None, kept_clean=0, found_inf=None, row_live=None, row_live_bytes=None):
         super().__init__(int(walk_mode), int(fast_bin), int(walk_groups_per_cu), int(lane_perm),
                          int(kept_clean), None if trace is None else ptr(trace),
                          None if found_inf is None else ptr(found_inf),
-                         None if row_live is None else ptr(row_live))
+                         None if row_live is None else ptr(row_live),
+                         None if row_live_bytes is None else ptr(row_live_bytes))
 
 
 def _opts_ref(opts):

@@ -106,6 +106,14 @@ __device__ __forceinline__ uint64_t trace_hw_id() {
 #define DFHIP_WALK_MODE_DEFAULT -1
 #endif
 
+// The liveness mask of the gradient rows: one bit per row
+// (dfhip_binned_opts.row_live) or one byte per row (row_live_bytes); at most
+// one of the two is set, both null: every row is live.
+struct RowLive {
+    const uint32_t *bits;
+    const uint8_t *bytes;
+};
+
 // The per-call options (dfhip_binned_opts, NULL = defaults) resolved once per
 // call; the library keeps no mode state between calls.
 struct Opts {
@@ -116,7 +124,7 @@ struct Opts {
     bool clean;           // the counts scratch's totals / plan words are zero on entry
     uint64_t *trace;      // debug walk timeline or null
     float *found_inf;     // the sum flags a non-finite value it writes (null: no check)
-    const uint32_t *row_live;  // one bit per gradient row, 0: not filed (null: all live)
+    RowLive row_live;     // the rows' liveness mask, bits or bytes (both null: all live)
 };
 
 static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
@@ -127,8 +135,12 @@ static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
     r.clean = false;
     r.trace = nullptr;
     r.found_inf = nullptr;
-    r.row_live = nullptr;
+    r.row_live = RowLive{nullptr, nullptr};
     if (!o) return true;
+    if (o->row_live && o->row_live_bytes) {
+        set_error("binned backward: row_live and row_live_bytes are exclusive");
+        return false;
+    }
     if (o->walk_mode < -1 || o->walk_mode > 1) {
         set_error("binned backward: walk_mode must be -1, 0 or 1 (got %d)",
                   (int)o->walk_mode);
@@ -146,7 +158,7 @@ static bool resolve_opts(const dfhip_binned_opts *o, Opts &r) {
     r.clean = o->kept_clean > 0;
     r.trace = o->trace;
     r.found_inf = o->found_inf;
-    r.row_live = o->row_live;
+    r.row_live = RowLive{o->row_live, o->row_live_bytes};
     return true;
 }
 
@@ -312,11 +324,13 @@ __device__ __forceinline__ void append(const uint64_t (&mask)[W], uint32_t b0, u
     }
 }
 
-// Liveness bit of gradient row r (dfhip_binned_opts.row_live; null: every row
-// is live).  A dead row's gradient row is all zero: it is not filed, so the
-// walk never sees it, and the sums are what they were (it added w * 0).
-__device__ __forceinline__ bool row_is_live(const uint32_t *__restrict__ live, uint32_t r) {
-    return !live || ((live[r >> 5] >> (r & 31u)) & 1u) != 0u;
+// Liveness of gradient row r (dfhip_binned_opts.row_live / row_live_bytes; both
+// null: every row is live).  A dead row's gradient row is all zero: it is not
+// filed, so the walk never sees it, and the sums are what they were (it added
+// w * 0).
+__device__ __forceinline__ bool row_is_live(const RowLive &live, uint32_t r) {
+    if (live.bytes) return live.bytes[r] != 0;  // uniform
+    return !live.bits || ((live.bits[r >> 5] >> (r & 31u)) & 1u) != 0u;
 }
 
 // The walk's plan must not notice a mask: the bin totals that deal out the walk parts
@@ -347,7 +361,7 @@ __global__ __launch_bounds__(1024) void k_bin(const float *__restrict__ inputs,
                                              SliceDyn dyn, float inv, uint32_t B,
                                              uint32_t *__restrict__ counts,
                                              uint16_t *__restrict__ entries,
-                                             const uint32_t *__restrict__ row_live) {
+                                             RowLive row_live) {
     __shared__ uint32_t cnt[kMaxBins];
     __shared__ uint32_t dead[kMaxBins];  // entries of dead rows, not filed (see count_dead)
     const bool align = align_corners != 0;
@@ -539,7 +553,7 @@ __global__ __launch_bounds__(1024) void k_bin_fast(const float *__restrict__ inp
                                                   SliceDyn dyn, float inv, uint32_t B,
                                                   uint32_t *__restrict__ counts,
                                                   uint16_t *__restrict__ entries,
-                                                  const uint32_t *__restrict__ row_live,
+                                                  RowLive row_live,
                                                   Stencil st = Stencil{0.0f, 0.0f}) {
     __shared__ uint32_t cnt[kMaxBins];
     // single samples: entries of dead rows, counted for the plan's totals but
@@ -1910,7 +1924,7 @@ static int binned_backward(const char *name, int phase, int grad_dtype, const vo
             return DFHIP_EINVAL;
         }
     }
-    if (group != 1 && op.row_live) {
+    if (group != 1 && (op.row_live.bits || op.row_live.bytes)) {
         set_error("%s: row_live applies to single samples (group 1); stencil groups take no "
                   "mask", name);
         return DFHIP_EINVAL;

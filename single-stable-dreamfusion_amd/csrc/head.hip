@@ -389,6 +389,7 @@ struct RayChainArgs {
     float ent_lambda;
     float *grad_sigmas;
     void *grad_rgbs;
+    uint8_t *row_live;  // k_ray_chain<rgb_t, true>: one liveness byte per sample row
 };
 
 // One lane's sample of a 16-sample window as loaded (`in`: inside the ray).
@@ -434,7 +435,11 @@ template <typename rgb_t> __device__ __forceinline__ WinOps win_ops(const RawWin
     STEP(0) STEP(1) STEP(2) STEP(3) STEP(4) STEP(5) STEP(6) STEP(7) STEP(8) STEP(9) STEP(10) \
     STEP(11) STEP(12) STEP(13) STEP(14) STEP(15)
 
-template <typename rgb_t>
+// LIVE: the sample rows' liveness mask for the binned embedding backward is
+// written too (an instantiation of its own, so the kernel without a mask has
+// no mask code): this kernel makes the dead rows, and holds every row's four
+// gradient values as it stores them.
+template <typename rgb_t, bool LIVE = false>
 __global__ __launch_bounds__(kThreads) void k_ray_chain(RayChainArgs p) {
     __shared__ W w;
     __shared__ alignas(16) float s_x[kRays][kIn + 1];
@@ -543,13 +548,22 @@ __global__ __launch_bounds__(kThreads) void k_ray_chain(RayChainArgs p) {
     const float gr = g[0], gg = g[1], gb = g[2];
 #define DFHIP_SAMPLE_GRAD(I, WL, TL, RL, GL, BL, DT, CR, CG, CB)                              \
     {                                                                                         \
-        grad_rgbs[3 * (I) + 0] = rm::grad_cast<float, rgb_t>(gr * (WL));                      \
-        grad_rgbs[3 * (I) + 1] = rm::grad_cast<float, rgb_t>(gg * (WL));                      \
-        grad_rgbs[3 * (I) + 2] = rm::grad_cast<float, rgb_t>(gb * (WL));                      \
+        const rgb_t c0 = rm::grad_cast<float, rgb_t>(gr * (WL));                              \
+        const rgb_t c1 = rm::grad_cast<float, rgb_t>(gg * (WL));                              \
+        const rgb_t c2 = rm::grad_cast<float, rgb_t>(gb * (WL));                              \
+        grad_rgbs[3 * (I) + 0] = c0;                                                          \
+        grad_rgbs[3 * (I) + 1] = c1;                                                          \
+        grad_rgbs[3 * (I) + 2] = c2;                                                          \
         float acc = fmaf(gr, fmaf((TL), (CR), -(rf - (RL))), gg * fmaf((TL), (CG), -(gf - (GL)))); \
         acc = fmaf(gb, fmaf((TL), (CB), -(bf - (BL))), acc);                                  \
         acc = fmaf(gw, 1.0f - wsv, acc);                                                      \
-        p.grad_sigmas[(I)] = (DT) * acc;                                                      \
+        const float gs = (DT) * acc;                                                          \
+        p.grad_sigmas[(I)] = gs;                                                              \
+        /* live iff one of the four values as stored compares unequal to zero  */             \
+        /* (-0.0 is zero, a NaN is live): k_field_bwd<LIVE>'s test             */             \
+        if constexpr (LIVE)                                                                   \
+            p.row_live[(I)] = (gs != 0.0f || to_f(c0) != 0.0f || to_f(c1) != 0.0f ||          \
+                               to_f(c2) != 0.0f) ? 1 : 0;                                     \
     }
     uint32_t done = 0;  // samples taken (the reference loop's final i)
     rm::BwdChain b;
@@ -577,6 +591,7 @@ __global__ __launch_bounds__(kThreads) void k_ray_chain(RayChainArgs p) {
             grad_rgbs[3 * row] = (rgb_t)0.0f;
             grad_rgbs[3 * row + 1] = (rgb_t)0.0f;
             grad_rgbs[3 * row + 2] = (rgb_t)0.0f;
+            if constexpr (LIVE) p.row_live[row] = 0;
         }
     }
     // 8. / 9.
@@ -976,16 +991,16 @@ extern "C" int dfhip_ray_head_forward_backward_entropy_loss_check(
                              stream, loss, &io, found_inf, defer_sum != 0);
 }
 
-extern "C" int dfhip_ray_chain_train(
-    int rgb_dtype, const float *sigmas, const void *rgbs, const float *deltas,
+// row_live: the liveness bytes of dfhip_ray_chain_train_live, or null
+static int ray_chain_train(
+    const char *name, int rgb_dtype, const float *sigmas, const void *rgbs, const float *deltas,
     const int32_t *rays, uint32_t M, uint32_t N, float T_thresh, float *ws, float *depth,
     float *image, const float *rays_d, const float *nears, const float *fars, const float *w1,
     const float *b1, const float *w2, const float *b2, float *out_image, float *out_depth,
     uint8_t *mask, const float *g_image, float *grad_image, float *grad_ws, float *partial,
     float *gw1, float *gb1, float *gw2, float *gb2, const float *grad_loss, float lambda,
     float *loss, float *found_inf, int defer_sum, float *grad_sigmas, void *grad_rgbs,
-    dfhip_stream_t stream) {
-    const char *name = "ray_chain_train";
+    uint8_t *row_live, dfhip_stream_t stream) {
     if (N == 0) {
         set_error("%s: N must be > 0", name);
         return DFHIP_EINVAL;
@@ -1000,12 +1015,15 @@ extern "C" int dfhip_ray_chain_train(
     const hd::RayChainArgs a{sigmas, rgbs, deltas, rays, M, N, T_thresh, ws, depth, image,
                              rays_d, nears, fars, w1, b1, w2, b2, out_image, out_depth, mask,
                              g_image, grad_image, grad_ws, partial, grad_loss, lambda,
-                             grad_sigmas, grad_rgbs};
+                             grad_sigmas, grad_rgbs, row_live};
     hipStream_t s = as_stream(stream);
     const uint32_t blocks = ceil_div(N, (uint32_t)hd::kRays);
-    if (rgb_dtype == DFHIP_F32) hd::k_ray_chain<float><<<blocks, hd::kThreads, 0, s>>>(a);
-    else if (rgb_dtype == DFHIP_F16) hd::k_ray_chain<half_t><<<blocks, hd::kThreads, 0, s>>>(a);
-    else if (rgb_dtype == DFHIP_BF16) hd::k_ray_chain<bf16_t><<<blocks, hd::kThreads, 0, s>>>(a);
+#define DFHIP_RAY_CHAIN(T)                                                            \
+    (row_live ? hd::k_ray_chain<T, true> : hd::k_ray_chain<T, false>)                 \
+        <<<blocks, hd::kThreads, 0, s>>>(a)
+    if (rgb_dtype == DFHIP_F32) DFHIP_RAY_CHAIN(float);
+    else if (rgb_dtype == DFHIP_F16) DFHIP_RAY_CHAIN(half_t);
+    else if (rgb_dtype == DFHIP_BF16) DFHIP_RAY_CHAIN(bf16_t);
     else {
         set_error("%s: rgb dtype must be f32, f16 or bf16 (got %d)", name, rgb_dtype);
         return DFHIP_EDTYPE;
@@ -1015,6 +1033,43 @@ extern "C" int dfhip_ray_chain_train(
         hd::k_head_wsum<<<ceil_div((uint32_t)hd::kParams, 64u) + 1u, 1024, 0, s>>>(
             partial, blocks, gw1, gb1, gw2, gb2, ws, N, lambda, loss, found_inf);
     return check_launch(name);
+}
+#undef DFHIP_RAY_CHAIN
+
+extern "C" int dfhip_ray_chain_train(
+    int rgb_dtype, const float *sigmas, const void *rgbs, const float *deltas,
+    const int32_t *rays, uint32_t M, uint32_t N, float T_thresh, float *ws, float *depth,
+    float *image, const float *rays_d, const float *nears, const float *fars, const float *w1,
+    const float *b1, const float *w2, const float *b2, float *out_image, float *out_depth,
+    uint8_t *mask, const float *g_image, float *grad_image, float *grad_ws, float *partial,
+    float *gw1, float *gb1, float *gw2, float *gb2, const float *grad_loss, float lambda,
+    float *loss, float *found_inf, int defer_sum, float *grad_sigmas, void *grad_rgbs,
+    dfhip_stream_t stream) {
+    return ray_chain_train("ray_chain_train", rgb_dtype, sigmas, rgbs, deltas, rays, M, N,
+                           T_thresh, ws, depth, image, rays_d, nears, fars, w1, b1, w2, b2,
+                           out_image, out_depth, mask, g_image, grad_image, grad_ws, partial, gw1,
+                           gb1, gw2, gb2, grad_loss, lambda, loss, found_inf, defer_sum,
+                           grad_sigmas, grad_rgbs, nullptr, stream);
+}
+
+extern "C" int dfhip_ray_chain_train_live(
+    int rgb_dtype, const float *sigmas, const void *rgbs, const float *deltas,
+    const int32_t *rays, uint32_t M, uint32_t N, float T_thresh, float *ws, float *depth,
+    float *image, const float *rays_d, const float *nears, const float *fars, const float *w1,
+    const float *b1, const float *w2, const float *b2, float *out_image, float *out_depth,
+    uint8_t *mask, const float *g_image, float *grad_image, float *grad_ws, float *partial,
+    float *gw1, float *gb1, float *gw2, float *gb2, const float *grad_loss, float lambda,
+    float *loss, float *found_inf, int defer_sum, float *grad_sigmas, void *grad_rgbs,
+    uint8_t *row_live_bytes, dfhip_stream_t stream) {
+    if (!row_live_bytes) {
+        set_error("ray_chain_train_live: null row_live_bytes");
+        return DFHIP_EINVAL;
+    }
+    return ray_chain_train("ray_chain_train_live", rgb_dtype, sigmas, rgbs, deltas, rays, M, N,
+                           T_thresh, ws, depth, image, rays_d, nears, fars, w1, b1, w2, b2,
+                           out_image, out_depth, mask, g_image, grad_image, grad_ws, partial, gw1,
+                           gb1, gw2, gb2, grad_loss, lambda, loss, found_inf, defer_sum,
+                           grad_sigmas, grad_rgbs, row_live_bytes, stream);
 }
 
 extern "C" int dfhip_param_grad_sums(const float *mlp_partial, uint32_t mlp_parts, float *gw1,

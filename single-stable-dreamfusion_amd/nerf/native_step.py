@@ -32,7 +32,9 @@ report a non-finite value themselves, so the optimizer launches no check
 (fold_overflow_check); the optimizer's finalize stores the live sample count
 into model.step_counter (store_live_count); compositing, the ray head and the
 compositing backward are one launch, dfhip_ray_chain_train (fused_ray_chain,
-tests/test_gpu_ray_chain.py).
+tests/test_gpu_ray_chain.py).  That launch also writes the liveness mask of
+the rows it zeroes, so the field backward runs without its mask code
+(chain_live_mask, tests/test_gpu_chain_live.py).
 
 Every launch sits in a _dfhip.timed region with its algorithmic bytes (the
 regions are no-ops unless a kernel timer is installed, and the graph is
@@ -229,7 +231,14 @@ class NativeAlbedoStep:
         # one of their own: they pass none
         self.live_mask = (bool(getattr(trainer, "live_mask", True)) and trainer.fused_backward
                           and not self.stencil_bin)
-        self.row_live = torch.zeros((fcap + 31) // 32, **i32)
+        self._row_live_bits = torch.zeros((fcap + 31) // 32, **i32)
+        # the albedo one-launch ray chain makes the dead rows and writes the mask
+        # itself, one byte per row (trainer.chain_live_mask): the field backward
+        # then runs without its mask code.  Set by body()
+        self.chain_live = False
+        self._launcher_chain_live = False  # the form the embedding launcher was built for
+        self.row_live_bytes = (torch.zeros(cap, dtype=torch.uint8, device=dev)
+                               if self.live_mask and not self.shade_code else None)
         sc = trainer.scaler
         if sc.is_enabled() and sc._scale is None:
             sc._lazy_init_scale_growth_tracker(dev)  # what scaler.scale() does on first use
@@ -429,17 +438,24 @@ class NativeAlbedoStep:
         # one pass): the per-ray chain never leaves its sixteen lanes
         chain = defer and bool(getattr(self.trainer, "fused_ray_chain", True))
         self.ray_chain = chain  # (tests: which form the captured step took)
+        self.chain_live = (chain and self.live_mask and self.row_live_bytes is not None
+                           and bool(getattr(self.trainer, "chain_live_mask", True)))
+        if self._emb_launch is not None and self.chain_live != self._launcher_chain_live:
+            # the embedding backward's launcher holds the other mask's pointer
+            self._emb_launch = self._emb_launch2 = None
         if chain:
+            live = (ptr(self.row_live_bytes),) if self.chain_live else ()
             with T("ray_chain", (32 + 120 + 44) * N, md,
-                   (4 + 3 * hb + 8) + (4 + 3 * hb + 8 + 4 + 3 * hb)):
-                call("dfhip_ray_chain_train", _dfhip._DTYPE[rgb.dtype], ptr(self.sigma), ptr(rgb),
+                   (4 + 3 * hb + 8) + (4 + 3 * hb + 8 + 4 + 3 * hb) + len(live)):
+                call("dfhip_ray_chain_train" + ("_live" if live else ""),
+                     _dfhip._DTYPE[rgb.dtype], ptr(self.sigma), ptr(rgb),
                      ptr(self.deltas), ptr(self.rays), cap, N, 1e-4, ptr(self.ws),
                      ptr(self.depth), ptr(self.image), ptr(self.rays_d), ptr(self.nears),
                      ptr(self.fars), *[ptr(w) for w in bw], ptr(self.out_image),
                      ptr(self.out_depth), ptr(self.mask), ptr(self.g_image),
                      ptr(self.grad_image), ptr(self.grad_ws), ptr(self.head_partial),
                      *[ptr(g) for g in self._bg_grads()], ptr(scale), self.lam, ptr(self.loss),
-                     ptr(fi), 1, ptr(self.grad_sigma), ptr(self.grad_albedo), stream())
+                     ptr(fi), 1, ptr(self.grad_sigma), ptr(self.grad_albedo), *live, stream())
             return self._field_backward(fi, defer, hb)
         # compositing (raymarching.py:238-269)
         with T("composite_rays_train_forward", 32 * N, md, 4 + 3 * hb + 8):
@@ -526,7 +542,8 @@ class NativeAlbedoStep:
                 self.encoder.offsets, self.rows, S, Hb, gridtype, align, None, None,
                 _parts(self.rows, self.C), self.m_field, found_inf=fi,
                 defer_sum=self.merged_sums,
-                row_live=self.row_live if self.live_mask else None)
+                row_live=(self._row_live_bits if self.live_mask and not self.chain_live
+                          else None))
             if self.merged_sums:
                 # one launch: the field's sum, the head's (deferred above) and
                 # the entropy loss, each in its own fixed order
@@ -630,9 +647,28 @@ class NativeAlbedoStep:
         o.kept_clean = 1 if getattr(self.trainer, "kept_clean_scratch", True) else 0
         # the sum reports a non-finite gradient it writes (folded overflow check)
         o.found_inf = ptr(self.found_inf)
-        # rows the field backward marked dead are not filed
-        o.row_live = ptr(self.row_live) if self.live_mask else None
+        # rows the field backward (bits) or the ray chain (bytes) marked dead
+        # are not filed
+        bits = self.live_mask and not self.chain_live
+        o.row_live = ptr(self._row_live_bits) if bits else None
+        o.row_live_bytes = ptr(self.row_live_bytes) if self.chain_live else None
+        # the launcher keeps these pointers: body() drops it if the form changes
+        self._launcher_chain_live = self.chain_live
         return o
+
+    @property
+    def row_live(self):
+        """The last step's liveness mask, one bit per field row (bit r & 31 of
+        int32 word r >> 5; zero from the live count on): the field backward's
+        buffer, or packed here from the ray chain's bytes (chain_live)."""
+        if not self.chain_live:
+            return self._row_live_bits
+        m = int(self.m_field[0])
+        bits = torch.zeros(self._row_live_bits.numel() * 32, dtype=torch.int64,
+                           device=self.row_live_bytes.device)
+        bits[:m] = self.row_live_bytes[:m] != 0
+        words = (bits.view(-1, 32) << torch.arange(32, device=bits.device)).sum(1)
+        return words.to(torch.int32)  # (two's complement wrap of bit 31)
 
     def time_field(self, reps=5):
         """Eager re-launches of the last step's fused field forward and MLP

@@ -342,6 +342,9 @@ class Trainer(object):
         #    launch (dfhip_ray_chain_train; albedo, one pass, with the merged
         #    sums)
         self.fused_ray_chain = True
+        #  - the liveness mask written by the ray chain (a byte per row,
+        #    dfhip_ray_chain_train_live) instead of the field backward
+        self.chain_live_mask = True
         # graph-replayed steps through the reference-API modules (no native
         # step, model.fused_field False): the host-count march, then a graph
         # per sample-count bucket (nerf/graph.py BucketedModuleStep)
